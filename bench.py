@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the ABCD-VAE training step (ABCD-VAE/learning.py:147-163) on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4|c5] [--dump-outputs DIR] [--full]
 
 Metric (BASELINE.json): segments/sec/node for a full training step
 (encoder -> sampler -> KL -> decoder -> loss -> backward -> all-reduce ->
@@ -12,12 +12,23 @@ K = 128, hidden 256, bi-LSTM encoder, self-feedback LSTM decoder, Gumbel
 sampling on, N = 10,000.  Inputs are resident in HBM before the timed region;
 noise is drawn in-kernel (Philox).
 
-Besides the one JSON line the driver reads, it reports
+A plain run sets up, warms up, times the K steps and prints the one JSON line
+the driver reads (``ms_per_step`` = milliseconds per timed step).
+``--dump-outputs DIR`` also writes what the last timed step left its caller
+(the scalar vector, the updated flat parameters, the flat gradient, the
+encoder's last hidden states and the sampled features) as float32
+``DIR/<name>.npy``; weights, batches and the Philox seeds are fixed, so two
+builds run with the same arguments see identical inputs.
+
+With ``--full`` the line also reports (each in runs of its own, after the
+timed region)
   roofline     -- FP32-MFMA roofline of the dominant kernel family, timed live
                   with HIP events (see DESIGN.md §Measurement);
   cpu_baseline -- the CPU oracle (oracle/abcd_oracle.py, a torch-CPU
                   restatement of the reference step) timed on a bounded sample
-                  on this host (rank 0, N = 1 only).
+                  on this host, and the parity anchor against it (rank 0,
+                  N = 1 only);
+  allreduce_us_per_step -- the gradient all-reduce timed alone (N > 1 only).
 For N > 1 the driver launches it under torch.distributed.run (one rank per
 GPU, RCCL, WORLD_SIZE set).  Run by hand as ``bench.py --gpus N`` without a
 WORLD_SIZE, the process starts that same launcher as a CHILD (N fresh worker
@@ -290,6 +301,11 @@ def main():
     ap.add_argument("--batches", type=int, default=4, help="distinct synthetic batches cycled per rank")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the kernel roofline, the CPU baseline and its "
+                         "parity anchor, the all-reduce alone (--no-cpu-baseline / --no-kernel-timing drop one)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     cfg = CONFIGS[args.config]
     explicit = args.gpus is not None
@@ -348,6 +364,8 @@ def main():
     # a persistent kernel that timed out invalidates the run (outside the timed region)
     from modules import _native as N
     N.raise_on_status(N.lib().abcd_device_status(), "bench")
+    if args.dump_outputs and rank == 0:  # before anything below steps the model again
+        dump_outputs(args.dump_outputs, step)
     segs = world * cfg["B"] * args.steps
     value = segs / elapsed
     ms = elapsed / args.steps * 1e3
@@ -367,10 +385,11 @@ def main():
     }
     if world > 1:
         out["config"]["rccl_world_size"] = dist.get_world_size()
-        out["allreduce_us_per_step"] = allreduce_time(step)
-    if not args.no_kernel_timing:
+        if args.full:
+            out["allreduce_us_per_step"] = allreduce_time(step)
+    if args.full and not args.no_kernel_timing:
         out["roofline"] = kernel_roofline(step, batches, cfg, run, args.config)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"], parity = cpu_baseline(cfg, args.config, device)
         out["recon_loss_rel_delta"] = parity["recon_loss_rel_delta"]
         out["parity"] = parity
@@ -378,6 +397,29 @@ def main():
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, step):
+    """What the last timed step left its caller, as float32 <path>/<name>.npy:
+    the scalar vector step() returned (engine.EM .. STATUS), the flat
+    parameters after the SGD update, the flat gradient it applied, and the
+    encoder's last hidden states / the sampled features of the step's batch.
+    An array over its share of DUMP_BUDGET_BYTES is written as a fixed
+    (seed 0) sorted sample of its flattened elements."""
+    import numpy as np
+    outs = {"scalars": step.scalars, "params": step.flat.flat, "grads": step.flat.grad,
+            "last_hidden": step.last_hidden, "feats": step.feats}
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BUDGET_BYTES // len(outs) - 4096) // 4  # float32 elements per file, room for the .npy header
+    for name, t in outs.items():
+        a = t.detach().to("cpu", torch.float32).contiguous().numpy()
+        if a.size > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def allreduce_time(step, reps=10):

@@ -16,7 +16,7 @@ run() {  # name spec cmd...
 for k in 1 2 3; do
 for v in "$@"; do
 name=${v%%=*}; spec=${v#*=}
-run $name $spec timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/b_${name}_$k.json 2> $OUT/b_${name}_$k.err
+run $name $spec timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $OUT/b_${name}_$k.json 2> $OUT/b_${name}_$k.err
 python -c "import json;d=json.load(open('$OUT/b_${name}_$k.json'));print('$name', d['ms_per_step'], {k:round(v['avg_launch_us']) for k,v in d['roofline']['all_kernels'].items()})"
 done
 done

@@ -15,10 +15,10 @@ if [ "$PART" = "1" ]; then
   timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $OUT/smoke.log 2>&1
   tail -1 $OUT/smoke.log
   for c in c2 c4 c5 c5gru; do
-    timeout -k 10 300 python -u bench.py --config $c --steps 20 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err
+    timeout -k 10 300 python -u bench.py --config $c --steps 20 --warmup 3 --full > $OUT/bench_$c.json 2> $OUT/bench_$c.err
     echo "bench $c done"
   done
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2 -o run -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_prof_c2.json 2> $OUT/prof_c2.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c2 -o run -- python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline > $OUT/bench_prof_c2.json 2> $OUT/prof_c2.err
   python scripts/step_timeline.py $(find $OUT/prof_c2 -name "run_kernel_trace.csv" | head -1) > $OUT/step_timeline_c2.txt
   python scripts/queue_gaps.py $(find $OUT/prof_c2 -name "run_kernel_trace.csv" | head -1) > $OUT/queue_gaps_c2.txt
   echo "part 1 done"

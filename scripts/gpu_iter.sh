@@ -16,7 +16,7 @@ for rep in 1 2; do
   for setting in "$@"; do
     k=$((k + 1))
     e=$setting; [ "$e" = "-" ] && e=""
-    env $e timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/b_$k.json 2> $OUT/b_$k.err
+    env $e timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $OUT/b_$k.json 2> $OUT/b_$k.err
     python -c "import json;d=json.load(open('$OUT/b_$k.json'));print('[$setting]', d['ms_per_step'], {k:v['avg_launch_us'] for k,v in d['roofline']['all_kernels'].items()})"
   done
 done
