@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Assemble profiles/parity_errors.json from one GPU suite run.
+
+    ABCD_PARITY_DUMP=<dir> python -m pytest -m gpu tests
+    python scripts/parity_table.py <dir>
+
+tests/test_gpu_edges.py, test_gpu_fullshape.py and test_gpu_prod.py write the
+errors they observed (the HIP path against the float64 / fp32 oracle or the
+reference's fixtures) into <dir> when ABCD_PARITY_DUMP is set; this puts them
+into one table next to the tolerances derived from them.
+"""
+import glob
+import json
+import os
+import re
+import sys
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+
+
+def sig(x, n=3):
+    return float(f"{x:.{n - 1}e}")
+
+
+def main(src):
+    import test_gpu_edges as TE
+    import test_gpu_fullshape as TF
+    import test_gpu_prod as TP
+    edges, full, prod = {}, {}, {}
+    worst_ratio = {}
+    for path in sorted(glob.glob(os.path.join(src, "*.json"))):
+        name = os.path.basename(path)[:-5]
+        with open(path) as f:
+            d = json.load(f)
+        if name.startswith("fullshape-"):
+            full[name[len("fullshape-"):]] = dict(
+                clip=sig(d["clip"]), worst={m: sig(x) for m, x in d["worst"].items()},
+                tensors={k: {m: sig(x) for m, x in v.items()} for k, v in d["tensors"].items()})
+        elif name.startswith("prod-"):
+            prod[name[len("prod-"):]] = dict(
+                worst=sig(d["worst"]), **({"clip": sig(d["clip"])} if "clip" in d else {}),
+                tensors={k: {m: sig(x) for m, x in v.items()} for k, v in d.get("tensors", {}).items()})
+        else:
+            rows = {}
+            for r in d:
+                rows[r["tensor"]] = [sig(r["e32_rel"]), sig(r["e_hip_rel"]), sig(r["e32_blk"]), sig(r["e_hip_blk"]), r["R"]]
+                k = r["tensor"]
+                for a, b in ((r["e_hip_rel"], r["e32_rel"]), (r["e_hip_blk"], r["e32_blk"])):
+                    if a > TE.bound(k, b, R=TE.R_DEFAULT):  # past the default bound
+                        worst_ratio[k] = max(worst_ratio.get(k, 0.0), sig(a / max(b, 1e-30)))
+            edges[name] = rows
+    table = {
+        "what": "errors of the HIP path observed in one `pytest -m gpu tests` run on MI355X (scripts/parity_table.py)",
+        "edge_cases": {
+            "columns": ["e32_rel", "e_hip_rel", "e32_blk", "e_hip_blk", "R"],
+            "metrics": "rel = max|a - ref| / max|ref|; blk = edge_cases.block_err (worst 16 x 16 block, floor 1e-2); "
+                       "ref = the float64 oracle; e32 = the fp32 oracle, e_hip = the GPU. g/ gradients, d/ post-SGD "
+                       "deltas (e32 = the gradient's + the norm's; the stored parameter's half-ulp taken off e_hip), "
+                       "norm = the clip norm (relative)",
+            "bound": "e_hip <= R * e32 + 1e-7, and e_hip <= %g whatever R" % TE.HARD,
+            "R_default": TE.R_DEFAULT, "R_tensor": TE.R_TENSOR,
+            "worst_ratio_past_R_default": worst_ratio,
+            "R_note": "R is raised only for a tensor past the default bound, to at most 2 x its own worst ratio. "
+                      + TE.R_NOTE,
+            "worst_e_hip": {m: max(r[i] for rows in edges.values() for r in rows.values())
+                            for m, i in (("rel", 1), ("blk", 3))} if edges else {},
+            "cases": edges,
+        },
+        "full_shape": {
+            "file": "tests/test_gpu_fullshape.py", "reference": "the fp32 oracle (oracle.train_step)",
+            "metrics": "rel / blk / norm: a gradient against the oracle's; sgd: the post-SGD delta less the stored "
+                       "parameter's 2 ulp; clip: the global norm",
+            "GRAD_TOL": TF.GRAD_TOL, "BLOCK_TOL": TF.BLOCK_TOL, "GRAD_TOL_before": 1e-3,
+            "derivation": "3 x the worst observed in the file, rounded up to one significant digit",
+            "worst": {m: max(c["worst"][m] for c in full.values()) for m in ("rel", "blk", "norm", "sgd")} if full else {},
+            "cases": full,
+        },
+        "prod_fixtures": {
+            "file": "tests/test_gpu_prod.py", "reference": "tests/golden/prod_*.npz (the reference's own step)",
+            "metrics": "every figure GRAD_TOL multiplies: gradient norm, whole gradient (rel), row / column sums, "
+                       "post-SGD delta norm and sum",
+            "GRAD_TOL": TP.GRAD_TOL, "GRAD_TOL_before": 1e-3,
+            "derivation": "3 x the worst observed in the file, rounded up to one significant digit",
+            "worst": max(c["worst"] for c in prod.values()) if prod else None,
+            "cases": prod,
+        },
+    }
+    out = os.path.join(REPO, "profiles", "parity_errors.json")
+    text = json.dumps(table, indent=1)
+    # one line per tensor: collapse the arrays of numbers
+    text = re.sub(r"\[\s+([^\[\]{}]*?)\s+\]", lambda m: "[" + re.sub(r"\s+", " ", m.group(1)) + "]", text)
+    with open(out, "w") as f:
+        f.write(text + "\n")
+    print(out, os.path.getsize(out), "bytes;", len(edges), "edge cases,", len(full), "full-shape,", len(prod), "prod")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])

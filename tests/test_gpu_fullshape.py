@@ -17,9 +17,11 @@ reference's fixtures in ``tests/golden``):
   grid 256``, 16 encoder groups = ``grid 256``);
 * em / off / kl / loss within 1e-4 relative (north star);
 * logits within 1e-4 of their max, argmax categories identical;
-* every parameter gradient within 1e-3 of its own max (norms 1e-3 relative);
+* every parameter gradient within 3e-5 of its own max (norms 3e-5 relative)
+  and within 4e-5 in its worst 16 x 16 block (``edge_cases.block_err``): 3 x
+  the worst observed, every tensor's figures reported (``-rA``);
 * the global gradient norm (clip) within 1e-4, post-SGD parameters within
-  1e-3 of each tensor's update.
+  3e-5 of each tensor's update.
 
 Reference: ``ABCD-VAE/modules/model.py:53,60-66,165-196,581-639``,
 ``ABCD-VAE/learning.py:155-163``.
@@ -30,6 +32,7 @@ import sys
 import pytest
 import torch
 
+from edge_cases import block_err, dump_observed
 from gpu_helpers import named_params, rel_err
 
 pytestmark = pytest.mark.gpu
@@ -37,7 +40,12 @@ pytestmark = pytest.mark.gpu
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 LOSS_TOL = 1e-4
-GRAD_TOL = 1e-3
+# 3 x the worst figure observed in this file on MI355X (profiles/parity_errors.json), rounded up to one digit:
+# gradients 9.5e-6 of a tensor's max (c5 B = 512), norms 7.9e-7, post-SGD deltas 9.2e-6 -> 3e-5 (was 1e-3);
+# the worst 16 x 16 block (edge_cases.block_err) 1.29e-5 -> 4e-5
+GRAD_TOL = 3e-5
+BLOCK_TOL = 4e-5
+
 
 KERNELS = {
     "LSTM": ("enc_fwd_persist<4,16,8>", "enc_bwd_w8<4>", "dec_fwd_x6<13,8,8,LSTM>", "dec_bwd_w16<9,LSTM>"),
@@ -60,7 +68,7 @@ def _oracle_cfg(O, cfg):
 
 
 @pytest.mark.parametrize("name,B,seed", CASES)
-def test_full_shape_step_vs_oracle(name, B, seed):
+def test_full_shape_step_vs_oracle(name, B, seed, record_property):
     sys.path.insert(0, REPO)
     import bench
     from oracle import abcd_oracle as O
@@ -112,9 +120,12 @@ def test_full_shape_step_vs_oracle(name, B, seed):
     assert rel_err(step.feats, out["feats"]) < 1e-4
     if not cfg["plain"]:
         assert torch.equal(logits.argmax(-1).cpu(), out["logits"].argmax(-1))
+    seen = {}  # tensor -> the observed figures (reported with -rA, kept in profiles/parity_errors.json)
     for k, p in named.items():
         gh = step.flat.grad_of(p).detach().double().cpu()
         gr = grads[k].double()
+        seen[k] = dict(rel=rel_err(gh, gr), blk=block_err(gh, gr),
+                       norm=abs(float(gh.norm()) - float(gr.norm())) / max(float(gr.norm()), 1e-30))
         assert abs(float(gh.norm()) - float(gr.norm())) <= GRAD_TOL * float(gr.norm()) + 1e-12, \
             (k, float(gh.norm()), float(gr.norm()))
         assert rel_err(gh, gr) < GRAD_TOL, (k, rel_err(gh, gr))
@@ -122,26 +133,42 @@ def test_full_shape_step_vs_oracle(name, B, seed):
     step.optimizer_step(lr=1.0, momentum=0.0, clip=1.0)
     torch.cuda.synchronize()
     assert abs(float(step.scalars[engine.NORM]) - total) <= 1e-4 * total, (float(step.scalars[engine.NORM]), total)
+    clip = abs(float(step.scalars[engine.NORM]) - total) / total
+    sgd_bad = []
     for k, p in named.items():
         # the update is formed in fp32 on both sides (p - lr * coef * g): besides
-        # 1e-3 of the update itself, allow the rounding of the stored parameter
+        # GRAD_TOL of the update itself, allow the rounding of the stored parameter
         # (2 ulp of its largest entry) -- the clipped update is ~1e-4 of p here
         dh = p.detach().double().cpu() - init[k].double().cpu()
         dr = new[k].double() - P[k].double()
-        tol = GRAD_TOL * float(dr.abs().max()) + 2 * 2.0 ** -23 * float(P[k].abs().max())
-        assert float((dh - dr).abs().max()) <= tol, (k, float((dh - dr).abs().max()), tol)
+        ulp = 2 * 2.0 ** -23 * float(P[k].abs().max())
+        tol = GRAD_TOL * float(dr.abs().max()) + ulp
+        err = float((dh - dr).abs().max())
+        seen[k]["sgd"] = max(err - ulp, 0.0) / max(float(dr.abs().max()), 1e-30)  # the part GRAD_TOL has to cover
+        if not err <= tol:
+            sgd_bad.append((k, err, tol))
+    for k, v in seen.items():
+        print(f"{name}-B{B} {k}: rel {v['rel']:.2e} blk {v['blk']:.2e} norm {v['norm']:.2e} sgd {v['sgd']:.2e}")
+    worst = {m: max(v[m] for v in seen.values()) for m in ("rel", "blk", "norm", "sgd")}
+    print(f"{name}-B{B} worst: " + " ".join(f"{m} {x:.2e}" for m, x in worst.items()) + f" clip {clip:.2e}")
+    record_property("parity_errors", dict(case=f"{name}-B{B}", clip=clip, worst=worst, tensors=seen))
+    dump_observed(f"fullshape-{name}-B{B}", dict(clip=clip, worst=worst, tensors=seen))
+    assert not sgd_bad, sgd_bad
+    for k, v in seen.items():
+        assert v["blk"] < BLOCK_TOL, (k, v["blk"])
 
 
 def test_side_gate_released_by_per_step_encoder_backward(monkeypatch):
     """A batch past the persistent kernels' resident capacity (B = 544: 17
     encoder BPTT groups x 2 directions x 8 members = 272 workgroups > 256 CUs)
-    runs the per-step encoder backward.  The training step still queues the
-    side-stream gate (it waits for the NEXT encoder BPTT to be resident), so
-    the per-step encoder backward must release it itself; otherwise the
-    decoder's weight gradients wait out the gate's spin bound (~0.1 s) every
-    step.  Checked: the dispatch is the per-step one, the step with
-    the gate on is no slower than with it off (ABCD_SIDE_GATE=0) beyond noise,
-    and both give the same loss."""
+    runs the per-step encoder backward.  The training step arms the
+    side-stream gate around its decoder backward, but the gate kernel is only
+    queued when a persistent encoder BPTT was launched since the arming
+    (side_gate(): target 0 queues nothing); with the per-step encoder backward
+    there is nothing to wait for, so the decoder's weight gradients must not
+    wait out the gate's spin bound every step.  Checked: the
+    dispatch is the per-step one, the step with the gate on is no slower than
+    with it off (ABCD_SIDE_GATE=0) beyond noise, and both give the same loss."""
     import time
     sys.path.insert(0, REPO)
     import bench

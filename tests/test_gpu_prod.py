@@ -10,13 +10,15 @@ and asserts which kernels ran (abcd_dispatch_name), so the template instances
 bench.py times at config 2 / 4 / 5 are the ones compared with the reference.
 
 Tolerances: loss terms 1e-4 relative (north star), logits / last hidden 1e-4
-of the tensor's max, gradients 1e-3 of the tensor's max (norms 1e-3
-relative), post-SGD parameter deltas 1e-3, argmax categories exact."""
+of the tensor's max, gradients 5e-5 of the tensor's max (norms 5e-5
+relative), post-SGD parameter deltas 5e-5 (3 x the worst observed; every
+tensor's figures are reported with -rA), argmax categories exact."""
 import os
 
 import pytest
 import torch
 
+from edge_cases import dump_observed
 from golden_io import PROD, load_prod, prod_inputs
 from gpu_helpers import named_params, rel_err
 from test_prod_fixtures import build_product
@@ -24,7 +26,9 @@ from test_prod_fixtures import build_product
 pytestmark = pytest.mark.gpu
 
 LOSS_TOL = 1e-4
-GRAD_TOL = 1e-3
+# 3 x the worst figure observed in this file on MI355X (profiles/parity_errors.json), rounded up to one digit:
+# 1.57e-5 (lstm_k128, a gradient's row sums; whole gradients <= 1.1e-6 of a tensor's max) -> 5e-5 (was 1e-3)
+GRAD_TOL = 5e-5
 
 # the kernels bench.py's configs dispatch at H = Hm = 256, F = 129 (Fp = 144)
 EXPECT = {
@@ -41,7 +45,7 @@ def _noise(inp):
 
 
 @pytest.mark.parametrize("name", PROD)
-def test_fused_step_prod_vs_reference(name):
+def test_fused_step_prod_vs_reference(name, record_property):
     from modules import engine, noise, _native as N
     meta, arr = load_prod(name)
     enc, samp, dec = build_product(meta, "cuda")
@@ -72,24 +76,38 @@ def test_fused_step_prod_vs_reference(name):
     assert rel_err(step.feats, arr["feats"]) < 1e-4
     if not meta.get("plain"):
         assert torch.equal(logits.argmax(-1).cpu(), arr["logits"].argmax(-1))
+    seen = {}  # tensor -> the observed figures, each in units of what GRAD_TOL multiplies
     for k, p in named.items():
         g = step.flat.grad_of(p).detach().double().cpu()
+        seen[k] = {}
         if "gn/" + k in arr:
             ref = float(arr["gn/" + k])
+            seen[k]["norm"] = abs(float(g.norm()) - ref) / max(ref, 1e-30)
             assert abs(float(g.norm()) - ref) <= GRAD_TOL * ref + 1e-12, (k, float(g.norm()), ref)
         if "g/" + k in arr:
+            seen[k]["rel"] = rel_err(g, arr["g/" + k])
             assert rel_err(g, arr["g/" + k]) < GRAD_TOL, (k, rel_err(g, arr["g/" + k]))
         if "grow/" + k in arr:
+            seen[k]["rowsum"] = rel_err(g.sum(1), arr["grow/" + k])
+            seen[k]["colsum"] = rel_err(g.sum(0), arr["gcol/" + k])
             assert rel_err(g.sum(1), arr["grow/" + k]) < GRAD_TOL, k
             assert rel_err(g.sum(0), arr["gcol/" + k]) < GRAD_TOL, k
     step.optimizer_step(lr=meta["lr"], momentum=0.0, clip=meta["clip"])
     torch.cuda.synchronize()
     assert abs(float(step.scalars[engine.NORM]) - float(arr["total_norm"])) <= 1e-4 * float(arr["total_norm"])
+    clip = abs(float(step.scalars[engine.NORM]) - float(arr["total_norm"])) / float(arr["total_norm"])
     for k, p in named.items():
         delta = (p.detach().double().cpu() - init[k].double().cpu())
         ref_n, ref_s = float(arr["dq_norm/" + k]), float(arr["dq_sum/" + k])
+        seen[k]["sgd_norm"] = abs(float(delta.norm()) - ref_n) / max(ref_n, 1e-30)
+        seen[k]["sgd_sum"] = abs(float(delta.sum()) - ref_s) / max(ref_n * delta.numel() ** 0.5, 1e-30)
+        print(f"{name} {k}: " + " ".join(f"{m} {x:.2e}" for m, x in seen[k].items()))
         assert abs(float(delta.norm()) - ref_n) <= GRAD_TOL * ref_n + 1e-9, (k, float(delta.norm()), ref_n)
         assert abs(float(delta.sum()) - ref_s) <= GRAD_TOL * ref_n * delta.numel() ** 0.5 + 1e-9, k
+    worst = max(x for v in seen.values() for x in v.values())
+    print(f"{name} worst (any figure under GRAD_TOL) {worst:.2e} clip {clip:.2e}")
+    record_property("parity_errors", dict(case="prod_" + name, clip=clip, worst=worst, tensors=seen))
+    dump_observed("prod-" + name, dict(clip=clip, worst=worst, tensors=seen))
 
 
 @pytest.mark.parametrize("name", ["lstm_k128", "gru_k1024_spk", "plain_lstm"])
@@ -219,5 +237,8 @@ def test_fused_step_wide_decoder_separate_offset_head():
     sc = sc.cpu()
     for i, k in ((engine.EM, "em"), (engine.OFF, "off"), (engine.KL, "kl"), (engine.LOSS, "loss")):
         assert abs(float(sc[i]) - float(out[k])) <= 1e-4 * abs(float(out[k])) + 1e-5, (k, float(sc[i]), float(out[k]))
+    worst = max(rel_err(step.flat.grad_of(p), grads[k]) for k, p in named.items())
+    print(f"wide decoder: worst gradient rel_err {worst:.2e}")
+    dump_observed("prod-wide_decoder", dict(worst=worst))
     for k, p in named.items():
         assert rel_err(step.flat.grad_of(p), grads[k]) < GRAD_TOL, (k, rel_err(step.flat.grad_of(p), grads[k]))
