@@ -346,6 +346,46 @@ int abcd_decoder_backward_params(const abcd_decoder_cfg* cfg, const abcd_decoder
                                  const abcd_decoder_grads* g, void* ws, size_t ws_bytes, void* stream,
                                  void* wgrad_stream);
 
+/* Free-running generation with learned stopping: what the reference's eval-mode
+ * decoder loop (model.py:147-196 with no ground truth, sampler2mean for the
+ * mean) would give if it cut each row where the offset predictor
+ * (model.py:121-122,191) first fires, instead of at a length the caller knows.
+ * Decoder rows are independent, so the forward runs on the full B x T_max
+ * rectangle (abcd_decoder_forward's kernels, batch_sizes[t] = B) and the rows
+ * are cut afterwards; the steps a row runs past its stop are the price.
+ * features: B x feature_size; speakers: int64 B (or NULL).
+ * mode ABCD_GEN_MEAN: the mean is emitted and fed back (run as eps = 0: out
+ *   equals mu); eps, seed and offset are ignored.
+ * mode ABCD_GEN_SAMPLE: the sample is fed back; eps: B*T_max x F standard
+ *   normals in rectangle (time-major) order, or NULL -> Philox(seed, offset)
+ *   as abcd_decoder_forward draws it.
+ * cfg->feedback must be 1 (generation is eval mode).
+ * Row b's length is max(min_len, t* + 1) with t* the first step whose offset
+ * logit is > stop_logit (the firing frame is the segment's last, as is_offset
+ * marks it in training); T_max when none is; a NaN logit never fires.
+ * 1 <= T_max <= ABCD_GEN_MAX_T (the ordering kernel's LDS histogram),
+ * min_len <= T_max, B <= ABCD_GEN_MAX_B (the stable rank is one workgroup's
+ * O(B^2) count), B * T_max < 2^31.
+ * Outputs: lengths[B] in input row order; order[B] = input row indices by
+ * length descending, ties in input order (stable); batch_sizes[T_max] = rows
+ * with length > t (0 past the longest row; DEVICE here, the caller copies it
+ * to the host for a PackedSequence); total[0] = the sum of the lengths; out,
+ * mu, log_var (x F) and offset_logits, each B*T_max rows or NULL, in
+ * PackedSequence.data order of the sorted rows: packed row off[t] + j holds
+ * step t of input row order[j] (off = exclusive scan of batch_sizes); rows at
+ * and past total[0] are unspecified.
+ * With abcd_timing_enable on, abcd_timing_read_kernel ids 8 / 9 / 10 read the
+ * gen_stop_scan / gen_order / gen_gather launches (3: the decoder forward). */
+enum abcd_gen_mode { ABCD_GEN_MEAN = 0, ABCD_GEN_SAMPLE = 1 };
+#define ABCD_GEN_MAX_T 4096
+#define ABCD_GEN_MAX_B 16384
+size_t abcd_decoder_generate_workspace_bytes(const abcd_decoder_cfg* cfg, int T_max, int B);
+int abcd_decoder_generate(const abcd_decoder_cfg* cfg, const abcd_decoder_params* p, const float* features,
+                          const int64_t* speakers, int B, int T_max, int mode, const float* eps, uint64_t seed,
+                          uint64_t offset, float stop_logit, int min_len, float* out, float* mu, float* log_var,
+                          float* offset_logits, int32_t* lengths, int64_t* order, int64_t* batch_sizes,
+                          int64_t* total, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence

@@ -193,7 +193,37 @@ struct Arena {
 
 // checks PackedSequence.batch_sizes (host): non-increasing, sum L, first B
 int validate_batch(const int64_t* bs, int T, int L, int B);
+
+// The decoder's workspace (abcd_rnn.hip), shared with abcd_generate.hip, which
+// runs the forward on a rectangle and reads its padded stashes.
+struct DecWS {
+  // derived weights
+  float *Wihp, *bcomb, *bgru, *W1cat, *b1cat, *W2mp, *W2lp, *b2mp, *b2lp;
+  float *WihTp, *WhhT, *W2mT, *W2lT, *W1catT, *W1oT, *Wf2hT;
+  // forward stash
+  float *FS, *Hinit, *Xin, *Hprev, *Cprev, *Gst, *Cst, *Hs, *Aact, *MU, *LV, *OUT, *Zo, *offlog, *dlog_raw, *bce;
+  float* offpart;  // the fused offset head's partial logits (L x offset_head_slices(Hm))
+  float* EPS;  // the Philox decoder noise, rows x F (philox_normal_fill)
+  float* dWb;  // [dW_ih | db] of the cell (bias column folded into the GEMM)
+  double* part;
+  // backward
+  float *dGX, *dGH, *DC, *DC0, *dH0, *dhid, *dFS, *DHO, *dMU, *dLV, *dZ, *dZo, *dlog_s;
+  int* off;          // device step offsets (persistent kernels)
+  unsigned* sync;    // persistent-kernel group counters
+  float* skp;        // dec_bwd_sk split-K partials
+  float* scratch;
+  size_t scratch_floats;
+};
+DecWS carve_decoder(Arena& A, const abcd_decoder_cfg* c, int T, int L, int B);
 }  // namespace abcd
+
+// the decoder forward behind abcd_decoder_forward_dropout / _split (abcd_rnn.hip);
+// sl: the stream of the loss reductions
+int dec_forward_impl(const abcd_decoder_cfg* c, const abcd_decoder_params* p, const abcd_packed* x,
+                     const float* features, const int64_t* speakers, const float* gt_offset, const float* eps,
+                     const float* xmask, uint64_t seed, uint64_t offset, float* flatten_out, float* mu_out,
+                     float* lv_out, float* offset_logits, float* losses, void* ws, size_t ws_bytes, void* stream,
+                     hipStream_t sl);
 
 namespace abcd {
 // Optional live timing of the recurrent kernel family (bench.py roofline):

@@ -1059,25 +1059,6 @@ __global__ void unpad_rows(const float* src, int Fp, float* dst, int F, long row
     dst[i] = src[(i / F) * Fp + (i % F)];
 }
 
-struct DecWS {
-  // derived weights
-  float *Wihp, *bcomb, *bgru, *W1cat, *b1cat, *W2mp, *W2lp, *b2mp, *b2lp;
-  float *WihTp, *WhhT, *W2mT, *W2lT, *W1catT, *W1oT, *Wf2hT;
-  // forward stash
-  float *FS, *Hinit, *Xin, *Hprev, *Cprev, *Gst, *Cst, *Hs, *Aact, *MU, *LV, *OUT, *Zo, *offlog, *dlog_raw, *bce;
-  float* offpart;  // the fused offset head's partial logits (L x offset_head_slices(Hm))
-  float* EPS;  // the Philox decoder noise, rows x F (philox_normal_fill)
-  float* dWb;  // [dW_ih | db] of the cell (bias column folded into the GEMM)
-  double* part;
-  // backward
-  float *dGX, *dGH, *DC, *DC0, *dH0, *dhid, *dFS, *DHO, *dMU, *dLV, *dZ, *dZo, *dlog_s;
-  int* off;          // device step offsets (persistent kernels)
-  unsigned* sync;    // persistent-kernel group counters
-  float* skp;        // dec_bwd_sk split-K partials
-  float* scratch;
-  size_t scratch_floats;
-};
-
 static int dec_check(const abcd_decoder_cfg* c) {
   if (!c || c->hidden_size <= 0 || c->hidden_size % 16 || c->mlp_hidden <= 0 || c->mlp_hidden % 16 ||
       c->feature_size <= 0 || c->feature_size % 16 || c->output_size <= 0 ||
@@ -1087,7 +1068,7 @@ static int dec_check(const abcd_decoder_cfg* c) {
   return 0;
 }
 
-static DecWS carve_decoder(Arena& A, const abcd_decoder_cfg* c, int T, int L, int B) {
+DecWS carve_decoder(Arena& A, const abcd_decoder_cfg* c, int T, int L, int B) {
   DecWS w{};
   const int H = c->hidden_size, Hm = c->mlp_hidden, F = c->output_size, Fp = rup16(F);
   const int G = c->rnn_type == ABCD_LSTM ? 4 : 3, GH = G * H;
@@ -1208,12 +1189,6 @@ extern "C" int abcd_decoder_forward(const abcd_decoder_cfg* c, const abcd_decode
                                       flatten_out, mu_out, lv_out, offset_logits, losses, ws, ws_bytes, stream);
 }
 
-static int dec_forward_impl(const abcd_decoder_cfg* c, const abcd_decoder_params* p, const abcd_packed* x,
-                            const float* features, const int64_t* speakers, const float* gt_offset, const float* eps,
-                            const float* xmask, uint64_t seed, uint64_t offset, float* flatten_out, float* mu_out,
-                            float* lv_out, float* offset_logits, float* losses, void* ws, size_t ws_bytes,
-                            void* stream, hipStream_t sl);
-
 extern "C" int abcd_decoder_forward_dropout(const abcd_decoder_cfg* c, const abcd_decoder_params* p,
                                             const abcd_packed* x, const float* features, const int64_t* speakers,
                                             const float* gt_offset, const float* eps, const float* xmask,
@@ -1235,11 +1210,11 @@ extern "C" int abcd_decoder_forward_split(const abcd_decoder_cfg* c, const abcd_
                           loss_stream ? (hipStream_t)loss_stream : (hipStream_t)stream);
 }
 
-static int dec_forward_impl(const abcd_decoder_cfg* c, const abcd_decoder_params* p, const abcd_packed* x,
-                            const float* features, const int64_t* speakers, const float* gt_offset, const float* eps,
-                            const float* xmask, uint64_t seed, uint64_t offset, float* flatten_out, float* mu_out,
-                            float* lv_out, float* offset_logits, float* losses, void* ws, size_t ws_bytes,
-                            void* stream, hipStream_t sl) {
+int dec_forward_impl(const abcd_decoder_cfg* c, const abcd_decoder_params* p, const abcd_packed* x,
+                     const float* features, const int64_t* speakers, const float* gt_offset, const float* eps,
+                     const float* xmask, uint64_t seed, uint64_t offset, float* flatten_out, float* mu_out,
+                     float* lv_out, float* offset_logits, float* losses, void* ws, size_t ws_bytes, void* stream,
+                     hipStream_t sl) {
   ABCD_REQUIRE(dec_check(c) == 0 && p && x && features && ws);
   ABCD_REQUIRE(!xmask || c->feedback);
   ABCD_REQUIRE(validate_batch(x->batch_sizes, x->T, x->L, x->B) == 0);

@@ -24,6 +24,8 @@ ABCD_EINVAL = 1000
 ABCD_MAX_LAYERS = 4
 LSTM, GRU = 0, 1
 SAMPLE_SOFTMAX, SAMPLE_GUMBEL = 0, 1
+GEN_MEAN, GEN_SAMPLE = 0, 1
+GEN_MAX_T, GEN_MAX_B = 4096, 16384
 
 
 class RnnW(ctypes.Structure):
@@ -137,6 +139,11 @@ _SIGS = {
     "abcd_decoder_backward_params": (c_int, [_P(DecoderCfg), _P(DecoderParams), _P(Packed), c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, _P(DecoderGrads),
                                              c_void_p, c_size_t, c_void_p, c_void_p]),
+    "abcd_decoder_generate_workspace_bytes": (c_size_t, [_P(DecoderCfg), c_int, c_int]),
+    "abcd_decoder_generate": (c_int, [_P(DecoderCfg), _P(DecoderParams), c_void_p, c_void_p, c_int, c_int, c_int,
+                                      c_void_p, c_uint64, c_uint64, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
     "abcd_stft_frames": (c_int, [ctypes.c_longlong, c_int, c_int, c_int]),
     "abcd_featurize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "abcd_featurize_packed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float,
@@ -218,7 +225,7 @@ def source_hash():
     import hashlib
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     names = ["abcd_gemm.hip", "abcd_rnn.hip", "abcd_persist.hip", "abcd_sampler.hip", "abcd_optim.hip",
-             "abcd_feat.hip", "abcd_common.h", "abcd_internal.h", "abcd_persist.h", "abcd_x6.h",
+             "abcd_feat.hip", "abcd_generate.hip", "abcd_common.h", "abcd_internal.h", "abcd_persist.h", "abcd_x6.h",
              "../../include/abcd_hip.h"]
     h = hashlib.sha256()
     for n in sorted(names):

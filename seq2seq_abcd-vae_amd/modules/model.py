@@ -637,6 +637,76 @@ class RNN_Variational_Decoder(torch.nn.Module):
                                                        ops._i64(seed), ops._i64(offset), xmask, params, cfg)
         return (em if gt is not None else None), (off if gt_off is not None else None), flat, (mu, lv), offl
 
+    def generate(self, features, max_length, speaker=None, mean=True, stop_prob=0.5, min_length=1, eps=None):
+        """Free-running generation: every row runs until the offset predictor's
+        probability first exceeds ``stop_prob`` (that frame is the row's last),
+        for at least ``min_length`` and at most ``max_length`` frames.
+
+        ``mean=True`` emits and feeds back the mean (the reference's
+        ``sampler2mean``); otherwise the sample, with noise ``eps``
+        (``B * max_length x F``, time-major rectangle) or, when None, from
+        ``modules/noise.py`` as ``forward`` draws it.  Runs in eval form (the
+        sample is always fed back) under ``torch.no_grad()``.
+
+        Returns ``(packed, lengths, (mu, log_var), offset_logits)``: ``packed``
+        is a ``PackedSequence`` of the emitted frames (rows sorted by length,
+        descending and stable; ``sorted_indices`` / ``unsorted_indices`` map to
+        the input rows) that ``RNN_Variational_Encoder`` takes as it is,
+        ``lengths`` is per input row, and the last three are packed alike."""
+        features = _f32c(features)
+        N.require_gpu(features)
+        B, T = int(features.shape[0]), int(max_length)
+        if not (1 <= T <= N.GEN_MAX_T and 1 <= B <= N.GEN_MAX_B):
+            raise ValueError(f"generate: max_length in 1..{N.GEN_MAX_T} and 1..{N.GEN_MAX_B} rows (got {T}, {B})")
+        min_length = min(max(int(min_length), 1), T)
+        p = float(stop_prob)
+        stop_logit = -math.inf if p <= 0.0 else math.inf if p >= 1.0 else math.log(p / (1.0 - p))
+        F = self.rnn_cell.cell.input_size
+        dev = features.device
+        with torch.no_grad():
+            seed = offset = 0
+            if mean:
+                eps = None
+            elif eps is None:
+                eps, seed, offset = _noise.decoder_eps([B] * T, F, dev)
+            if eps is not None:
+                eps = _f32c(eps.to(dev))
+                if tuple(eps.shape) != (B * T, F):
+                    raise ValueError(f"generate: eps must be {(B * T, F)}, got {tuple(eps.shape)}")
+            mp = _module_pad(self, "decoder")
+            params, cfg = self._param_list(), self._cfg_list(1)
+            if mp is not None:  # a size not a multiple of 16: the zero-padded twin (padding.py)
+                features, params, cfg = _pad.pad_cols(features, mp.dims.Ddp), mp.weights(params), mp.twin._cfg_list(1)
+            spk = None
+            if self.embed_speaker is not None:
+                if speaker is None:
+                    raise ValueError("generate: this decoder embeds speakers; speaker (B indices) is required")
+                spk = speaker.to(dev, torch.int64).contiguous()
+            L_ = N.lib()
+            c = ops._dec_cfg(cfg)
+            nbytes = L_.abcd_decoder_generate_workspace_bytes(c, T, B)
+            if nbytes == 0:
+                raise N.HipError("decoder generate: unsupported configuration")
+            ws = N.workspace(nbytes, dev)
+            out, mu, lv = (torch.empty(B * T, F, device=dev) for _ in range(3))
+            offl = torch.empty(B * T, device=dev)
+            lengths = torch.empty(B, dtype=torch.int32, device=dev)
+            order = torch.empty(B, dtype=torch.int64, device=dev)
+            counts = torch.empty(T + 1, dtype=torch.int64, device=dev)  # batch_sizes, then total
+            N.check(L_.abcd_decoder_generate(c, ops._dec_struct(cfg, params), N.ptr(features), N.ptr(spk), B, T,
+                                             N.GEN_MEAN if mean else N.GEN_SAMPLE, N.ptr(eps), ops._u64(seed),
+                                             ops._u64(offset), stop_logit, min_length, N.ptr(out), N.ptr(mu),
+                                             N.ptr(lv), N.ptr(offl), N.ptr(lengths), N.ptr(order), N.ptr(counts),
+                                             N.c_void_p(counts.data_ptr() + 8 * T), N.ptr(ws), ws.numel(), N.stream()),
+                    "decoder generate")
+            N.op_status.probe(dev, "decoder generate")
+            host = counts.cpu()  # the one host read: batch_sizes and total
+            total = int(host[T])
+            batch_sizes = host[:T][host[:T] > 0].clone()
+            unsorted = torch.empty_like(order).scatter_(0, order, torch.arange(B, device=dev))
+            packed = torch.nn.utils.rnn.PackedSequence(out[:total], batch_sizes, order, unsorted)
+            return packed, lengths.to(torch.int64), (mu[:total], lv[:total]), offl[:total]
+
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()
         return torch.tensor([int((lengths > t).sum()) for t in range(int(lengths.max()))], dtype=torch.int64)
