@@ -387,6 +387,57 @@ int abcd_decoder_generate(const abcd_decoder_cfg* cfg, const abcd_decoder_params
                           int64_t* total, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Per-segment ELBO terms: the losses above before they are summed over the
+ * batch.  The reference only ever forms the batch scalars (model.py:193-195,
+ * 608-639; learning.py:200-240 logs their per-epoch means).
+ *
+ * abcd_segment_losses: segment b (packed row order, b = 0 the longest) owns
+ * packed rows off[t] + b for every t with batch_sizes[t] > b.
+ *   seg_em[b]  = sum over those rows and F columns of
+ *                0.5 (log 2pi + lv + (y - mu)^2 e^-lv), y = x->data (L x F);
+ *   seg_off[b] = sum over those rows of max(x,0) - x y + log1p(e^-|x|),
+ *                x = offset_logits (L), y = gt_offset (L): both or neither;
+ *   seg_len[b] = the segment's length, the number of t with batch_sizes[t] > b.
+ * Each output (B entries) may be NULL.  mu / log_var: L rows with row strides
+ * ld_mu / ld_lv >= F floats (the L x F outputs of abcd_decoder_forward, or a
+ * padded stash); columns >= F and rows of other segments are not read.  The
+ * terms are those of abcd_decoder_forward's losses: fp32 terms, fp64 sums in a
+ * fixed order (no atomics: two calls on the same inputs agree bit for bit), one
+ * cast to fp32 per segment.  One launch, one 1024-thread workgroup per segment;
+ * the step offsets travel through ws (abcd_segment_losses_workspace_bytes, 0
+ * for an unsupported T > 16383) without a host synchronisation.
+ * ABCD_EINVAL (nothing is written): batch_sizes not non-increasing,
+ * batch_sizes[0] != B, L != sum batch_sizes, a stride below F, seg_em with
+ * x->data, mu or log_var NULL, seg_off without the logits, one of
+ * offset_logits / gt_offset alone.
+ *
+ * abcd_sampler_kl_rows: the per-row part of ABCDSampler.kl_divergence.  With
+ * elog = digamma(alpha) - digamma(sum alpha) as abcd_sampler_kl forms it,
+ *   rows[b]  = sum_k q log q - sum_k q elog[k], q = softmax(logits[b]) over the
+ *              first valid_categories columns (padding columns masked out);
+ *   prior[0] = Eq log q(pi) - Eq log p(pi), the batch-independent bracket;
+ * abcd_sampler_kl's scalar is prior[0] * B / entire_data_size + sum_b rows[b].
+ * plain: rows[b] = -0.5 sum_f (1 + lv - mu^2 - e^lv) of logits = [mean |
+ * log_var] (B x 2 feature_dim), prior[0] = 0.  One launch, one wave per row;
+ * num_categories <= 8192 (any size, no multiple of 16 needed).  The call keeps
+ * no stash: ws / ws_bytes are not used (NULL / 0 are fine) and a sampler
+ * workspace holding a forward's stash is left as it is.
+ *
+ * Neither entry point touches a device-global ticket word: both may run
+ * beside any other launch.  With abcd_timing_enable on,
+ * abcd_timing_read_kernel ids 11 / 12 read the seg_losses / kl_rows launches;
+ * abcd_dispatch_name(11 / 12) names them ("seg_losses<1024> grid 512",
+ * "kl_rows_seg<128,128> grid 128", "kl_rows_plain<16> grid 128").
+ * ---------------------------------------------------------------------- */
+size_t abcd_segment_losses_workspace_bytes(int T, int B);
+int abcd_segment_losses(const abcd_packed* x, const float* mu, long ld_mu, const float* log_var, long ld_lv,
+                        const float* offset_logits, const float* gt_offset, float* seg_em, float* seg_off,
+                        int32_t* seg_len, void* ws, size_t ws_bytes, void* stream);
+int abcd_sampler_kl_rows(const abcd_sampler_cfg* cfg, const abcd_sampler_params* p, const float* logits, int B,
+                         double entire_data_size, float* rows, float* prior, void* ws, size_t ws_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

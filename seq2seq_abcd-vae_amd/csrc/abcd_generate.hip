@@ -19,8 +19,8 @@
 
 namespace abcd {
 
-// abcd_timing_read_kernel ids of the three launches (timing only: they have no
-// dispatch record, so they sit past TK_N)
+// abcd_timing_read_kernel ids of the three launches (timing only: they keep no
+// dispatch record)
 enum { TK_GEN_SCAN = 8, TK_GEN_ORDER = 9, TK_GEN_GATHER = 10 };
 
 // offlog[t * B + b]: adjacent threads read adjacent rows of one step (coalesced).

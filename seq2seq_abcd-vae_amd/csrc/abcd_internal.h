@@ -233,7 +233,9 @@ enum TimedKernel {
   TK_STEP = 0, TK_ENC_FWD = 1, TK_ENC_BWD = 2, TK_DEC_FWD = 3, TK_DEC_BWD = 4,
   TK_SAMP_FWD = 5, TK_SAMP_BWD = 6,  // dispatch records only (no live timing)
   TK_ENC_WGRAD = 7,                  // the encoder's layer-0 weight-gradient route (dispatch record)
-  TK_N = 8
+  // 8 .. 10: the generation cut's launches (abcd_generate.hip, live timing only)
+  TK_SEG_LOSSES = 11, TK_KL_ROWS = 12,  // abcd_score.hip: live timing and dispatch records
+  TK_N = 13
 };
 bool timing_on();
 void timing_mark(hipStream_t s, int kid);

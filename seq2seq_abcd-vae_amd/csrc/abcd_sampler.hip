@@ -8,6 +8,7 @@
 // softmax / KL backward are one-wave-per-row kernels.
 #include "abcd_common.h"
 #include "abcd_internal.h"
+#include "abcd_special.h"
 
 #include <mutex>
 #include <vector>
@@ -16,35 +17,6 @@ namespace abcd {
 
 // learning.py:171-178 perplexities of rows of `ld` floats (first K = categories)
 int perplexities_ld(const float* logits, int B, int ld, int K, const float* psl, float* out, void* stream);
-
-// ---- special functions (fp64, x > 0) --------------------------------------
-DEV double digamma_d(double x) {
-  double r = 0.0;
-  while (x < 6.0) { r -= 1.0 / x; x += 1.0; }
-  const double f = 1.0 / (x * x);
-  return r + log(x) - 0.5 / x -
-         f * (1.0 / 12 - f * (1.0 / 120 - f * (1.0 / 252 - f * (1.0 / 240 - f * (1.0 / 132)))));
-}
-DEV double trigamma_d(double x) {
-  double r = 0.0;
-  while (x < 6.0) { r += 1.0 / (x * x); x += 1.0; }
-  const double f = 1.0 / (x * x);
-  return r + 1.0 / x + 0.5 * f +
-         (1.0 / x) * f * (1.0 / 6 - f * (1.0 / 30 - f * (1.0 / 42 - f * (1.0 / 30 - f * (5.0 / 66)))));
-}
-
-DEV float wave_sum(float v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-DEV float wave_max(float v) {
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-DEV double wave_sum_d(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // y = softmax((logits + g) / tau) per row (g = 0 for the plain softmax).
 // Rows have K columns of which the first Kv are categories; the padding
@@ -75,29 +47,6 @@ __global__ void sample_softmax_rows(const float* logits, int B, int K, int Kv, i
   s = wave_sum(s);
   const float is = 1.f / s;
   for (int k = lane; k < Kv; k += 64) y[k] *= is;
-}
-
-// Block reductions (blockDim = 64 x nw, nw <= 16); `sh` holds 16 doubles.
-// Every thread returns the block-wide value.
-DEV double block_sum_dd(double v, double* sh) {
-  const int nw = blockDim.x >> 6;
-  v = wave_sum_d(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < nw; ++i) t += sh[i];
-  return t;
-}
-DEV double block_max_dd(double v, double* sh) {
-  const int nw = blockDim.x >> 6;
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = sh[0];
-  for (int i = 1; i < nw; ++i) t = fmax(t, sh[i]);
-  return t;
 }
 
 // KL prior part (model.py:620-633), one block: p = softmax(psl),

@@ -426,6 +426,26 @@ class ABCDSampler(_SamplerBase):
         return ops.sampler_kl(_pad.pad_cols(logits, mp.dims.Kp), mp.weight(self.posterior_shape_logits), mp.cfg,
                               self._prior_value(), float(entire_data_size))[0]
 
+    def kl_rows(self, logits, entire_data_size):
+        """``kl_divergence`` before its sum over the batch: ``(rows, prior)``
+        with ``rows[b] = sum_k q log q - sum_k q Eq[log pi_k]`` (B values, the
+        logits' row order) and ``prior`` the batch-independent Dirichlet
+        bracket ``Eq log q(pi) - Eq log p(pi)`` (0-d), so that
+        ``kl_divergence(logits, N) == prior * B / N + rows.sum()``.
+        Forward-only, under ``torch.no_grad()``."""
+        logits = _f32c(logits)
+        N.require_gpu(logits)
+        mp = _module_pad(self, "sampler")
+        with torch.no_grad():
+            if mp is None:
+                rows, prior = ops.sampler_kl_rows(logits, self.posterior_shape_logits, self._cfg_list(),
+                                                  self._prior_value(), float(entire_data_size))
+            else:
+                rows, prior = ops.sampler_kl_rows(_pad.pad_cols(logits, mp.dims.Kp),
+                                                  mp.weight(self.posterior_shape_logits), mp.cfg, self._prior_value(),
+                                                  float(entire_data_size))
+        return rows, prior
+
     def log_pmf(self, targets, logits):
         return torch.nn.functional.cross_entropy(logits, targets, reduction="sum")
 
@@ -512,6 +532,25 @@ class Sampler(_SamplerBase):
             return self._kl_divergence(*parameters)
         mp = _module_pad(self, "sampler")
         return ops.sampler_kl(mv, None, self._cfg_list() if mp is None else mp.cfg, 1.0, 1.0)[0]
+
+    def kl_rows(self, parameters, entire_data_size=None):
+        """``kl_divergence`` before its sum over the batch: ``(rows, prior)``,
+        ``rows[b] = -0.5 sum_f (1 + lv - mu^2 - e^lv)`` and ``prior = 0`` (the
+        Gaussian prior has no batch-independent term; ``entire_data_size`` is
+        accepted for symmetry with ``ABCDSampler.kl_rows``).  Forward-only,
+        under ``torch.no_grad()``."""
+        mu, lv = parameters
+        mv = getattr(mu, "_abcd_mv", None)
+        mp = _module_pad(self, "sampler")
+        cfg = self._cfg_list() if mp is None else mp.cfg
+        if mv is None:  # parameters not produced by this module's forward: [mu | log_var] at their own width
+            mv = torch.cat([_f32c(mu), _f32c(lv)], -1)
+            cfg = self._cfg_list()
+            cfg[3], cfg[5], cfg[6] = int(mu.shape[1]), 0, 0
+        N.require_gpu(mv)
+        with torch.no_grad():
+            rows, prior = ops.sampler_kl_rows(mv, None, cfg, 1.0, 1.0)
+        return rows, prior
 
     def log_pdf(self, samples, parameters):
         return self._log_pdf(samples, *parameters)
@@ -706,6 +745,57 @@ class RNN_Variational_Decoder(torch.nn.Module):
             unsorted = torch.empty_like(order).scatter_(0, order, torch.arange(B, device=dev))
             packed = torch.nn.utils.rnn.PackedSequence(out[:total], batch_sizes, order, unsorted)
             return packed, lengths.to(torch.int64), (mu[:total], lv[:total]), offl[:total]
+
+    def score(self, features, batch_sizes, speaker=None, ground_truth_out=None, ground_truth_offset=None, mean=True,
+              eps=None):
+        """Per-segment losses: ``(em, off, lengths)``, B values each in the
+        batch's packed row order (row b = the b-th longest segment, as
+        ``pack_sequence`` orders them).  ``em[b]`` is segment b's share of
+        ``forward``'s emission NLL, ``off[b]`` of its end-prediction BCE (None
+        without ``ground_truth_offset``), ``lengths[b]`` its frame count; their
+        sums over b are ``forward``'s two scalars under the same noise.
+
+        Runs in eval form (the sample is fed back, no input dropout, as
+        ``generate``) under ``torch.no_grad()``.  ``mean=True`` feeds back the
+        mean (zero noise, the reference's ``sampler2mean``): a deterministic
+        score.  ``mean=False`` feeds back the sample drawn with ``eps`` (L x F,
+        packed order) or, when None, with noise from ``modules/noise.py`` as
+        ``forward`` draws it."""
+        if ground_truth_out is None:
+            raise ValueError("score: ground_truth_out (the packed L x F frames to score) is required")
+        if not torch.is_tensor(batch_sizes):
+            batch_sizes = torch.tensor([int(b) for b in batch_sizes], dtype=torch.int64)
+        features = _f32c(features)
+        N.require_gpu(features)
+        F = self.rnn_cell.cell.input_size
+        dev = features.device
+        with torch.no_grad():
+            gt = _f32c(ground_truth_out.to(dev))
+            gt_off = None if ground_truth_offset is None else _f32c(ground_truth_offset.to(dev))
+            L = int(gt.shape[0])
+            seed = offset = 0
+            if mean:
+                eps = torch.zeros(L, F, device=dev)
+            elif eps is None:
+                eps, seed, offset = _noise.decoder_eps(batch_sizes, F, dev)
+            if eps is not None:
+                eps = _f32c(eps.to(dev))
+                if tuple(eps.shape) != (L, F):
+                    raise ValueError(f"score: eps must be {(L, F)}, got {tuple(eps.shape)}")
+            spk = None
+            if self.embed_speaker is not None:
+                if speaker is None:
+                    raise ValueError("score: this decoder embeds speakers; speaker (B indices) is required")
+                spk = speaker
+            mp = _module_pad(self, "decoder")
+            params, cfg = self._param_list(), self._cfg_list(1)
+            if mp is not None:  # a size not a multiple of 16: the zero-padded twin (padding.py)
+                features, params, cfg = _pad.pad_cols(features, mp.dims.Ddp), mp.weights(params), mp.twin._cfg_list(1)
+            _em, _off, _flat, mu, lv, offl, _ws = ops.decoder(features, batch_sizes, spk, gt, gt_off, eps,
+                                                              ops._i64(seed), ops._i64(offset), None, params, cfg)
+            em, off, lengths = ops.segment_losses(gt, batch_sizes, mu, lv, offl if gt_off is not None else None,
+                                                  gt_off, F)
+        return em, (off if gt_off is not None else None), lengths.to(torch.int64)
 
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()

@@ -21,7 +21,12 @@ operator                   replaces (reference)                            C ent
 ``abcd::decoder_bwd``      its backward (emission + offset losses)         ``abcd_decoder_backward_dropout``
 ``abcd::linear``           ``MLP`` layers (Linear [+ Tanh]) model.py:316   ``abcd_linear``
 ``abcd::linear_bwd``       their backward                                  ``abcd_linear_backward``
+``abcd::segment_losses``   (none: per-segment emission NLL / offset BCE)   ``abcd_segment_losses``
+``abcd::sampler_kl_rows``  (none: per-row part of ``kl_divergence``)       ``abcd_sampler_kl_rows``
 =========================  ==============================================  =========================================
+
+The last two are forward-only (scoring): they have no autograd formula and
+raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
 configuration travels as an ``int[]`` in the C struct's field order, the
@@ -534,8 +539,106 @@ def _linear_backward(ctx, dy):
 linear.register_autograd(_linear_backward, setup_context=_linear_setup)
 
 
+# ----------------------------------------------------------------------------
+# per-segment scoring (forward-only)
+# ----------------------------------------------------------------------------
+def _forward_only(op, name):
+    """No autograd formula: an input that requires grad (with grad mode on)
+    raises here instead of silently returning constants."""
+    def setup(ctx, inputs, output):
+        raise RuntimeError(f"abcd::{name} is forward-only (per-segment scores have no gradient): call it under "
+                           "torch.no_grad() or on detached tensors")
+
+    def backward(ctx, *grads):
+        raise RuntimeError(f"abcd::{name} is forward-only (per-segment scores have no gradient)")
+
+    op.register_autograd(backward, setup_context=setup)
+
+
+@torch.library.custom_op("abcd::segment_losses", mutates_args=())
+def segment_losses(gt: Optional[Tensor], batch_sizes: Tensor, mu: Optional[Tensor], log_var: Optional[Tensor],
+                   offset_logits: Optional[Tensor], gt_offset: Optional[Tensor], F: int) -> List[Tensor]:
+    """-> [em (B), off (B), lengths (B, int32)] in packed row order: the
+    emission NLL of (gt, mu, log_var) (L x F each; zeros when one is None) and
+    the offset BCE of (offset_logits, gt_offset) (L each; zeros when one is
+    None) summed per segment, and the segments' lengths.  mu / log_var may be
+    row-strided views (stride(0) >= F, stride(1) == 1)."""
+    ref = next((t for t in (gt, mu, log_var, offset_logits, gt_offset) if t is not None), None)
+    if ref is None:
+        raise ValueError("segment_losses: no input tensor (the lengths alone follow from batch_sizes on the host)")
+    N.require_gpu(ref)
+    dev = ref.device
+    want_em = gt is not None and mu is not None and log_var is not None
+    want_off = offset_logits is not None and gt_offset is not None
+    gt = gt.contiguous() if want_em else None
+
+    def rows(t):  # a row-strided L x F view passes as it is; anything else is made contiguous
+        if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+            return t, t.stride(0)
+        t = t.contiguous()
+        return t, t.shape[1]
+    (mu, ldm), (log_var, ldl) = (rows(mu), rows(log_var)) if want_em else ((None, 0), (None, 0))
+    offset_logits = offset_logits.contiguous() if want_off else None
+    gt_offset = gt_offset.contiguous() if want_off else None
+    L_ = N.lib()
+    pk, bs = _packed(gt, batch_sizes, F)
+    if want_em and not (tuple(mu.shape) == tuple(log_var.shape) == (pk.L, int(F)) and gt.shape[1] == int(F)):
+        raise ValueError(f"segment_losses: gt, mu and log_var must be {(pk.L, int(F))}")
+    if want_off and not (offset_logits.numel() == gt_offset.numel() == pk.L):
+        raise ValueError(f"segment_losses: offset_logits and gt_offset must hold {pk.L} entries")
+    nbytes = L_.abcd_segment_losses_workspace_bytes(pk.T, pk.B)
+    if nbytes == 0:
+        raise N.HipError("segment_losses: unsupported number of steps")
+    ws = N.workspace(nbytes, dev)
+    em = torch.empty(pk.B, device=dev) if want_em else torch.zeros(pk.B, device=dev)
+    off = torch.empty(pk.B, device=dev) if want_off else torch.zeros(pk.B, device=dev)
+    lengths = torch.empty(pk.B, dtype=torch.int32, device=dev)
+    N.check(L_.abcd_segment_losses(pk, N.ptr(mu), ldm, N.ptr(log_var), ldl, N.ptr(offset_logits), N.ptr(gt_offset),
+                                   N.ptr(em) if want_em else None, N.ptr(off) if want_off else None, N.ptr(lengths),
+                                   N.ptr(ws), ws.numel(), N.stream()), "segment losses")
+    return [em, off, lengths]
+
+
+@segment_losses.register_fake
+def _(gt, batch_sizes, mu, log_var, offset_logits, gt_offset, F):
+    ref = next(t for t in (gt, mu, log_var, offset_logits, gt_offset) if t is not None)
+    B = int(batch_sizes[0]) if batch_sizes.numel() else 0
+    return [ref.new_empty(B, dtype=torch.float32), ref.new_empty(B, dtype=torch.float32),
+            ref.new_empty(B, dtype=torch.int32)]
+
+
+_forward_only(segment_losses, "segment_losses")
+
+
+@torch.library.custom_op("abcd::sampler_kl_rows", mutates_args=())
+def sampler_kl_rows(logits: Tensor, psl: Optional[Tensor], cfg: List[int], prior: float,
+                    entire_data_size: float) -> List[Tensor]:
+    """-> [rows (B), prior (0-d)]: ABCD rows[b] = sum_k q log q - sum_k q elog[k]
+    and the batch-independent Dirichlet bracket (kl = prior * B / N + rows.sum());
+    plain rows[b] = -0.5 sum_f (1 + lv - mu^2 - e^lv), prior = 0."""
+    N.require_gpu(logits)
+    logits = logits.contiguous()
+    B = logits.shape[0]
+    if logits.shape[1] != _logit_width(cfg):
+        raise ValueError(f"sampler_kl_rows: logits must be B x {_logit_width(cfg)}, got {tuple(logits.shape)}")
+    rows = torch.empty(B, device=logits.device)
+    pr = torch.empty((), device=logits.device)
+    N.check(N.lib().abcd_sampler_kl_rows(_samp_cfg(cfg), _samp_struct(cfg, [], None, psl, prior), N.ptr(logits), B,
+                                         float(entire_data_size), N.ptr(rows), N.ptr(pr), None, 0, N.stream()),
+            "sampler kl rows")
+    return [rows, pr]
+
+
+@sampler_kl_rows.register_fake
+def _(logits, psl, cfg, prior, entire_data_size):
+    return [logits.new_empty(logits.shape[0]), logits.new_empty(())]
+
+
+_forward_only(sampler_kl_rows, "sampler_kl_rows")
+
+
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
-       "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd")
+       "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows")
 
 
 def registered() -> Sequence[str]:
