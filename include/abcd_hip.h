@@ -438,6 +438,64 @@ int abcd_sampler_kl_rows(const abcd_sampler_cfg* cfg, const abcd_sampler_params*
                          void* stream);
 
 /* ------------------------------------------------------------------------
+ * Every segment against every category prototype.  The decoder feeds back its
+ * own output and never sees the ground truth, so with eps = 0 in eval form its
+ * mu / log_var / offset logit at step t depend on (features, speaker, t) only:
+ * decoding P feature vectors once as a P-row rectangle (abcd_decoder_forward
+ * with batch_sizes[t] = P) gives the emission parameters every segment would
+ * get under each of them, the prototypes.
+ *
+ * abcd_pairwise_nll: x is the packed batch (L x F, HOST batch_sizes) as
+ * abcd_segment_losses takes it, gt_offset its L offset targets.  The
+ * prototypes are a time-major rectangle, prototype p at step t in row t P + p:
+ * proto_mu / proto_lv with row strides ld_mu / ld_lv >= F floats,
+ * proto_offset_logits T_proto * P entries; T_proto >= x->T (a rectangle
+ * decoded for the longest batch serves shorter ones).  Rows at steps >= x->T
+ * and columns >= F are never read.  With len_b the number of t with
+ * batch_sizes[t] > b and off the exclusive scan of batch_sizes,
+ *   pair_em [b ld_pair + p] = sum_{t < len_b} sum_{f < F} 0.5 (log 2pi + lv[t,p,f]
+ *                             + (x[off_t + b, f] - mu[t,p,f])^2 e^-lv[t,p,f]);
+ *   pair_off[b ld_pair + p] = sum_{t < len_b} max(o,0) - o y + log1p(e^-|o|),
+ *                             o = proto_offset_logits[t P + p], y = gt_offset[off_t + b].
+ * Either output (B rows, ld_pair >= P) may be NULL.  fp32 terms; e^-lv, the
+ * softplus of the logit and 0.5 sum_f (log 2pi + lv) are formed once per staged
+ * prototype element, not per pair; one frame's F columns are summed in fp32,
+ * frames in fp64 in step order, one cast per result.  Workgroups take 32
+ * segments x 32 prototypes x 16 steps and write fp64 partials to ws, which a
+ * second launch sums in slice order: the order of every sum is a function of
+ * (len_b, F) alone, there are no atomics and no workgroup waits for another,
+ * and two calls on the same inputs agree bit for bit.
+ * abcd_pairwise_nll_workspace_bytes is 0 for T > 16383 or B * P >= 2^31.
+ * ABCD_EINVAL (nothing is written, checked before any launch): a batch_sizes
+ * abcd_segment_losses rejects, P < 1, T_proto < x->T, a stride below F,
+ * ld_pair < P, pair_em with x->data, proto_mu or proto_lv NULL, pair_off
+ * without gt_offset and proto_offset_logits, a missing or short workspace.
+ *
+ * abcd_pair_posterior: s[b,p] = log_weight[p] - pair_em[b,p] - pair_off[b,p]
+ * (a NULL log_weight or pair_off counts as 0), differences and log-sum-exp in
+ * fp64 (the NLLs are ~1e5 with gaps of order 1).  One wave per row, 1 <= P <=
+ * 2^20, no workspace.  Each output may be NULL:
+ *   log_evidence[b] = logsumexp_p s[b,p];  resp[b ld_resp + p] = exp(s[b,p] -
+ *   log_evidence[b]);  best[b] = the lowest index attaining the maximum;
+ *   best_prob[b] = resp[b, best[b]].
+ * A NaN or +inf NLL, or a NaN or -inf weight, excludes that prototype (resp
+ * exactly 0); a row with every prototype excluded gets log_evidence = -inf,
+ * best = -1, best_prob = 0, resp = 0.
+ *
+ * Neither entry point touches a device-global ticket word.  With
+ * abcd_timing_enable on, abcd_timing_read_kernel ids 13 / 14 read the pair_nll
+ * (both of its launches) / pair_posterior launches; abcd_dispatch_name(13 / 14)
+ * names them ("pair_nll<32x32x16> grid 4x16x7", "pair_posterior<128> grid 128").
+ * ---------------------------------------------------------------------- */
+size_t abcd_pairwise_nll_workspace_bytes(int T, int B, int P);
+int abcd_pairwise_nll(const abcd_packed* x, const float* gt_offset, int P, int T_proto, const float* proto_mu,
+                      long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                      float* pair_em, float* pair_off, long ld_pair, void* ws, size_t ws_bytes, void* stream);
+int abcd_pair_posterior(const float* pair_em, const float* pair_off, long ld_pair, int B, int P,
+                        const float* log_weight, float* log_evidence, int32_t* best, float* best_prob, float* resp,
+                        long ld_resp, void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

@@ -235,7 +235,8 @@ enum TimedKernel {
   TK_ENC_WGRAD = 7,                  // the encoder's layer-0 weight-gradient route (dispatch record)
   // 8 .. 10: the generation cut's launches (abcd_generate.hip, live timing only)
   TK_SEG_LOSSES = 11, TK_KL_ROWS = 12,  // abcd_score.hip: live timing and dispatch records
-  TK_N = 13
+  TK_PAIR_NLL = 13, TK_PAIR_POST = 14,  // abcd_pairwise.hip: live timing and dispatch records
+  TK_N = 15
 };
 bool timing_on();
 void timing_mark(hipStream_t s, int kid);

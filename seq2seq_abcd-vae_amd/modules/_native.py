@@ -149,6 +149,11 @@ _SIGS = {
                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "abcd_sampler_kl_rows": (c_int, [_P(SamplerCfg), _P(SamplerParams), c_void_p, c_int, c_double, c_void_p,
                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "abcd_pairwise_nll_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "abcd_pairwise_nll": (c_int, [_P(Packed), c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p,
+                                  c_void_p, c_void_p, c_long, c_void_p, c_size_t, c_void_p]),
+    "abcd_pair_posterior": (c_int, [c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_long, c_void_p]),
     "abcd_stft_frames": (c_int, [ctypes.c_longlong, c_int, c_int, c_int]),
     "abcd_featurize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "abcd_featurize_packed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float,
@@ -230,7 +235,7 @@ def source_hash():
     import hashlib
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     names = ["abcd_gemm.hip", "abcd_rnn.hip", "abcd_persist.hip", "abcd_sampler.hip", "abcd_optim.hip",
-             "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_common.h", "abcd_internal.h",
+             "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_common.h", "abcd_internal.h",
              "abcd_persist.h", "abcd_special.h", "abcd_x6.h", "../../include/abcd_hip.h"]
     h = hashlib.sha256()
     for n in sorted(names):
@@ -335,6 +340,7 @@ def workspace(nbytes, device):
 
 ENC_FWD, ENC_BWD, DEC_FWD, DEC_BWD, SAMP_FWD, SAMP_BWD, ENC_WGRAD = 1, 2, 3, 4, 5, 6, 7
 SEG_LOSSES, KL_ROWS = 11, 12  # abcd_segment_losses / abcd_sampler_kl_rows (timing and dispatch ids)
+PAIR_NLL, PAIR_POST = 13, 14  # abcd_pairwise_nll / abcd_pair_posterior (timing and dispatch ids)
 
 
 def dispatch():
@@ -343,7 +349,8 @@ def dispatch():
     return {r: (L.abcd_dispatch_name(k).decode(), int(L.abcd_dispatch_count(k)))
             for r, k in (("enc_fwd", ENC_FWD), ("enc_bwd", ENC_BWD), ("dec_fwd", DEC_FWD), ("dec_bwd", DEC_BWD),
                                 ("samp_fwd", SAMP_FWD), ("samp_bwd", SAMP_BWD), ("enc_wgrad", ENC_WGRAD),
-                                ("seg_losses", SEG_LOSSES), ("kl_rows", KL_ROWS))}
+                                ("seg_losses", SEG_LOSSES), ("kl_rows", KL_ROWS),
+                                ("pair_nll", PAIR_NLL), ("pair_post", PAIR_POST))}
 
 
 def ptr_array(tensors):

@@ -446,6 +446,18 @@ class ABCDSampler(_SamplerBase):
                                                   float(entire_data_size))
         return rows, prior
 
+    def expected_log_prior(self, entire_data_size):
+        """``E_q[log pi_k] = digamma(alpha_k) - digamma(sum alpha)`` (K values)
+        under the Dirichlet posterior ``alpha = softmax(posterior_shape_logits)
+        * N + a0`` of ``kl_divergence``: the log weights of the categories in
+        ``ops.pair_posterior``.  alpha is formed in fp32 as the reference forms
+        it, the digammas in float64 on the device (K numbers, not a hot path)."""
+        N.require_gpu(self.posterior_shape_logits)
+        with torch.no_grad():
+            alpha = (torch.softmax(self.posterior_shape_logits.detach().float(), -1) * float(entire_data_size)
+                     + self.prior_concentration.float()).double()
+            return (torch.digamma(alpha) - torch.digamma(alpha.sum())).float()
+
     def log_pmf(self, targets, logits):
         return torch.nn.functional.cross_entropy(logits, targets, reduction="sum")
 
@@ -796,6 +808,69 @@ class RNN_Variational_Decoder(torch.nn.Module):
             em, off, lengths = ops.segment_losses(gt, batch_sizes, mu, lv, offl if gt_off is not None else None,
                                                   gt_off, F)
         return em, (off if gt_off is not None else None), lengths.to(torch.int64)
+
+    def prototypes(self, features, length, speaker=None):
+        """The emission parameters every segment gets under each row of
+        ``features`` (P x feature_size, e.g. codebook columns): ``(mu, log_var,
+        offset_logits)`` of the P x ``length`` rectangle, time-major: ``length
+        x P x F`` (twice) and ``length x P``, views of the decoder's packed
+        outputs (prototype p at step t in packed row ``t * P + p``).  The decoder feeds back its own
+        output and never sees the ground truth, so with zero noise these depend
+        on (features, speaker, t) only: ``score(features=row p repeated)``
+        gives every segment exactly these per-step parameters.  Runs in eval
+        form under ``torch.no_grad()`` with eps = 0 (``score``'s ``mean=True``)."""
+        features = _f32c(features)
+        N.require_gpu(features)
+        P, T = int(features.shape[0]), int(length)
+        if P < 1 or T < 1:
+            raise ValueError(f"prototypes: at least one feature row and one step (got {P}, {T})")
+        F = self.rnn_cell.cell.input_size
+        dev = features.device
+        with torch.no_grad():
+            spk = None
+            if self.embed_speaker is not None:
+                if speaker is None:
+                    raise ValueError("prototypes: this decoder embeds speakers; speaker (P indices) is required")
+                spk = speaker
+            mp = _module_pad(self, "decoder")
+            params, cfg = self._param_list(), self._cfg_list(1)
+            if mp is not None:  # a size not a multiple of 16: the zero-padded twin (padding.py)
+                features, params, cfg = _pad.pad_cols(features, mp.dims.Ddp), mp.weights(params), mp.twin._cfg_list(1)
+            bsz = torch.full((T,), P, dtype=torch.int64)
+            _em, _off, _flat, mu, lv, offl, _ws = ops.decoder(features, bsz, spk, None, None,
+                                                              torch.zeros(P * T, F, device=dev), 0, 0, None, params,
+                                                              cfg)
+        return mu.view(T, P, F), lv.view(T, P, F), offl.view(T, P)
+
+    def score_against(self, prototypes, batch_sizes, ground_truth_out, ground_truth_offset=None):
+        """Every segment against every prototype: ``(em, off, lengths)`` with
+        ``em[b, p]`` the emission NLL of segment b (packed row order, as
+        ``score``) under prototype p of ``prototypes`` (what ``prototypes()``
+        returned, decoded for at least as many steps as the batch has),
+        ``off[b, p]`` the end-prediction BCE (None without
+        ``ground_truth_offset``) and ``lengths[b]`` the frame counts.  Column p
+        is what ``score`` returns for features = prototype p's row repeated,
+        ``mean=True``.  Forward-only, under ``torch.no_grad()``."""
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(ground_truth_out)
+        if not torch.is_tensor(batch_sizes):
+            batch_sizes = torch.tensor([int(b) for b in batch_sizes], dtype=torch.int64)
+        bs = batch_sizes.to("cpu", torch.int64)
+        T, F = int(bs.numel()), self.rnn_cell.cell.input_size
+        dev = mu.device
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= T):
+            raise ValueError(f"score_against: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P with T_proto >= {T}")
+        P = int(offl.shape[1])
+        with torch.no_grad():
+            gt = _f32c(ground_truth_out.to(dev))
+            gt_off = None if ground_truth_offset is None else _f32c(ground_truth_offset.to(dev))
+            em, off = ops.pairwise_nll(gt, bs, gt_off, mu.reshape(-1, F), lv.reshape(-1, F),
+                                       offl.reshape(-1) if gt_off is not None else None, P, F)
+            lengths = (bs[None, :] > torch.arange(int(bs[0]))[:, None]).sum(1).to(dev)
+        return em, (off if gt_off is not None else None), lengths
 
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()

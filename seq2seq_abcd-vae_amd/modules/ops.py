@@ -23,9 +23,11 @@ operator                   replaces (reference)                            C ent
 ``abcd::linear_bwd``       their backward                                  ``abcd_linear_backward``
 ``abcd::segment_losses``   (none: per-segment emission NLL / offset BCE)   ``abcd_segment_losses``
 ``abcd::sampler_kl_rows``  (none: per-row part of ``kl_divergence``)       ``abcd_sampler_kl_rows``
+``abcd::pairwise_nll``     (none: every segment x every prototype)         ``abcd_pairwise_nll``
+``abcd::pair_posterior``   (none: responsibilities, evidence, argmax)      ``abcd_pair_posterior``
 =========================  ==============================================  =========================================
 
-The last two are forward-only (scoring): they have no autograd formula and
+The last four are forward-only (scoring): they have no autograd formula and
 raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -637,8 +639,124 @@ def _(logits, psl, cfg, prior, entire_data_size):
 _forward_only(sampler_kl_rows, "sampler_kl_rows")
 
 
+def _rows(t):
+    """(tensor, row stride): a row-strided 2-d view passes as it is; anything else is made contiguous."""
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t, t.stride(0)
+    t = t.contiguous()
+    return t, t.shape[1]
+
+
+@torch.library.custom_op("abcd::pairwise_nll", mutates_args=())
+def pairwise_nll(gt: Optional[Tensor], batch_sizes: Tensor, gt_offset: Optional[Tensor], proto_mu: Optional[Tensor],
+                 proto_lv: Optional[Tensor], proto_offset_logits: Optional[Tensor], P: int, F: int) -> List[Tensor]:
+    """-> [em (B x P), off (B x P)]: every segment of the packed batch (gt L x
+    F, gt_offset L) against every prototype.  The prototypes are a time-major
+    rectangle, prototype p at step t in row t * P + p: proto_mu / proto_lv
+    (T_proto * P x F, row-strided views pass without a copy) and
+    proto_offset_logits (T_proto * P), T_proto >= the batch's steps.  em needs
+    (gt, proto_mu, proto_lv), off needs (gt_offset, proto_offset_logits); the
+    one whose inputs are absent is zeros."""
+    ref = next((t for t in (gt, gt_offset, proto_mu, proto_lv, proto_offset_logits) if t is not None), None)
+    if ref is None:
+        raise ValueError("pairwise_nll: no input tensor")
+    for t in (gt, gt_offset, proto_mu, proto_lv, proto_offset_logits):
+        if t is not None:
+            N.require_gpu(t)
+    dev = ref.device
+    P, F = int(P), int(F)
+    want_em = gt is not None and proto_mu is not None and proto_lv is not None
+    want_off = gt_offset is not None and proto_offset_logits is not None
+    if not (want_em or want_off):
+        raise ValueError("pairwise_nll: needs (gt, proto_mu, proto_lv) or (gt_offset, proto_offset_logits)")
+    if P < 1:
+        raise ValueError("pairwise_nll: P must be at least 1")
+    gt = gt.contiguous() if want_em else None
+    (mu, ldm), (lv, ldl) = (_rows(proto_mu), _rows(proto_lv)) if want_em else ((None, 0), (None, 0))
+    ol = proto_offset_logits.contiguous() if want_off else None
+    gt_offset = gt_offset.contiguous() if want_off else None
+    L_ = N.lib()
+    pk, bs = _packed(gt, batch_sizes, F)
+    rows = mu.shape[0] if want_em else ol.numel()
+    if rows % P or rows // P < pk.T:
+        raise ValueError(f"pairwise_nll: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {pk.T}, "
+                         f"got {rows}")
+    if want_em and not (tuple(mu.shape) == tuple(lv.shape) == (rows, F) and tuple(gt.shape) == (pk.L, F)):
+        raise ValueError(f"pairwise_nll: gt must be {(pk.L, F)}, proto_mu and proto_lv {(rows, F)}")
+    if want_off and not (gt_offset.numel() == pk.L and ol.numel() == rows):
+        raise ValueError(f"pairwise_nll: gt_offset must hold {pk.L} entries, proto_offset_logits {rows}")
+    nbytes = L_.abcd_pairwise_nll_workspace_bytes(pk.T, pk.B, P)
+    if nbytes == 0:
+        raise N.HipError("pairwise_nll: unsupported shape (more than 16383 steps, or B * P >= 2^31)")
+    ws = N.workspace(nbytes, dev)
+    em = torch.empty(pk.B, P, device=dev) if want_em else torch.zeros(pk.B, P, device=dev)
+    off = torch.empty(pk.B, P, device=dev) if want_off else torch.zeros(pk.B, P, device=dev)
+    N.check(L_.abcd_pairwise_nll(pk, N.ptr(gt_offset), P, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                                 N.ptr(em) if want_em else None, N.ptr(off) if want_off else None, P, N.ptr(ws),
+                                 ws.numel(), N.stream()), "pairwise nll")
+    return [em, off]
+
+
+@pairwise_nll.register_fake
+def _pairwise_nll_fake(gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, P, F):
+    ref = next(t for t in (gt, gt_offset, proto_mu, proto_lv, proto_offset_logits) if t is not None)
+    B = int(batch_sizes[0]) if batch_sizes.numel() else 0
+    return [ref.new_empty(B, int(P), dtype=torch.float32), ref.new_empty(B, int(P), dtype=torch.float32)]
+
+
+_forward_only(pairwise_nll, "pairwise_nll")
+
+
+@torch.library.custom_op("abcd::pair_posterior", mutates_args=())
+def pair_posterior(pair_em: Tensor, pair_off: Optional[Tensor], log_weight: Optional[Tensor]) -> List[Tensor]:
+    """-> [log_evidence (B), best (B, int32), best_prob (B), resp (B x P)] of the
+    scores s[b, p] = log_weight[p] - pair_em[b, p] - pair_off[b, p] (absent
+    terms count as 0), taken in fp64: log_evidence = logsumexp_p s, resp =
+    exp(s - log_evidence), best the lowest index of the maximum (-1 when every
+    prototype is excluded by a NaN / +inf NLL or a NaN / -inf weight)."""
+    N.require_gpu(pair_em)
+    if pair_em.dim() != 2 or pair_em.shape[0] < 1 or pair_em.shape[1] < 1:
+        raise ValueError(f"pair_posterior: pair_em must be B x P, got {tuple(pair_em.shape)}")
+    B, P = (int(v) for v in pair_em.shape)
+    dev = pair_em.device
+    em, ld = _rows(pair_em.float())
+    off = None
+    if pair_off is not None:
+        N.require_gpu(pair_off)
+        if tuple(pair_off.shape) != (B, P):
+            raise ValueError(f"pair_posterior: pair_off must be {(B, P)}, got {tuple(pair_off.shape)}")
+        off, ldo = _rows(pair_off.float())
+        if ldo != ld:  # one row stride serves both
+            em, off, ld = em.contiguous(), off.contiguous(), P
+    lw = None
+    if log_weight is not None:
+        N.require_gpu(log_weight)
+        if log_weight.numel() != P:
+            raise ValueError(f"pair_posterior: log_weight must hold {P} entries, got {log_weight.numel()}")
+        lw = log_weight.float().contiguous()
+    ev = torch.empty(B, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    bp = torch.empty(B, device=dev)
+    resp = torch.empty(B, P, device=dev)
+    N.check(N.lib().abcd_pair_posterior(N.ptr(em), N.ptr(off), ld, B, P, N.ptr(lw), N.ptr(ev), N.ptr(best), N.ptr(bp),
+                                        N.ptr(resp), P, N.stream()), "pair posterior")
+    return [ev, best, bp, resp]
+
+
+@pair_posterior.register_fake
+def _(pair_em, pair_off, log_weight):
+    B, P = pair_em.shape
+    e = pair_em.new_empty
+    return [e(B, dtype=torch.float32), e(B, dtype=torch.int32), e(B, dtype=torch.float32),
+            e(B, P, dtype=torch.float32)]
+
+
+_forward_only(pair_posterior, "pair_posterior")
+
+
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
-       "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows")
+       "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
+       "pairwise_nll", "pair_posterior")
 
 
 def registered() -> Sequence[str]:

@@ -86,45 +86,75 @@ class Scorer(learning.Learner):
                            save_path, batch_size=batch_size, finish=lambda: _native.op_status.sync("score_dataset"))
 
 
-def score_table(score_batch, dataset, save_path, batch_size=1, finish=None):
+# the table's columns after data_ix: (name, dtype), or (name, names) for the sum of other columns
+TABLE = ((("length", np.int64), ("category_ix", np.int64)) + tuple((k, np.float64) for k in _TERMS)
+         + (("total", _TERMS),))
+
+
+def score_table(score_batch, dataset, save_path, batch_size=1, finish=None, columns=TABLE, long_path=None,
+                long_columns=None):
     """Writes the table: ``score_batch(packed, is_offset, speaker)`` gives a
     batch's columns in packed row order, which the loader's ``ixs`` map back to
-    ``data_ix``.  The table goes to a temporary path and takes save_path (an
-    earlier output kept as .prev) only once every batch is written and
+    ``data_ix``.  ``columns`` lists what follows ``data_ix``: ``(name, dtype)``
+    for a column ``score_batch`` returns, ``(name, names)`` for the sum of
+    earlier columns.  The table goes to a temporary path and takes save_path
+    (an earlier output kept as .prev) only once every batch is written and
     ``finish()`` (the device status check) has passed, so an error part way
-    leaves nothing partial behind.  Returns the number of rows written."""
-    tmp_path = save_path + ".partial"
+    leaves nothing partial behind.  Returns the number of rows written.
+
+    ``long_path``: a second, long table written under the same discipline from
+    ``score_batch(...)["long"]``, a dict holding ``row`` (the packed row each
+    long row belongs to, mapped to ``data_ix`` here) and the ``long_columns``
+    (``(name, dtype)``), in the order the rows are to be written."""
+    paths = [(save_path, save_path + ".partial")]
+    if long_path is not None:
+        paths.append((long_path, long_path + ".partial"))
     ann = None
     if "label" in dataset.df_annotation.columns:
         ann = dataset.df_annotation.drop(columns=["onset_ix", "offset_ix", "length"])
+
+    def host(v):
+        return v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+
+    def with_annotation(table):
+        if ann is None:
+            return table
+        return pd.concat([table, ann.reindex(table["data_ix"].to_numpy()).reset_index(drop=True)], axis=1)
+
     header, written = True, 0
     try:
         for packed, is_offset, speaker, ixs in data_utils.DataLoader(dataset, batch_size=batch_size, shuffle=False):
-            cols = {k: (v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v))
-                    for k, v in score_batch(packed, is_offset, speaker).items()}
+            out = score_batch(packed, is_offset, speaker)
             ix = np.asarray(ixs, dtype=np.int64)
             table = pd.DataFrame({"data_ix": ix})
-            for k in ("length", "category_ix"):
-                table[k] = cols[k].astype(np.int64)
-            for k in _TERMS:
-                table[k] = cols[k].astype(np.float64)
-            table["total"] = table[list(_TERMS)].sum(axis=1)
+            for name, kind in columns:
+                if isinstance(kind, (tuple, list)):
+                    table[name] = table[list(kind)].sum(axis=1)
+                else:
+                    table[name] = host(out[name]).astype(kind)
             if len(table) != len(ix):
                 raise RuntimeError(f"score_batch returned {len(table)} rows for a batch of {len(ix)} segments")
-            if ann is not None:
-                table = pd.concat([table, ann.reindex(ix).reset_index(drop=True)], axis=1)
-            table.to_csv(tmp_path, index=False, mode="w" if header else "a", header=header)
+            mode = "w" if header else "a"
+            with_annotation(table).to_csv(paths[0][1], index=False, mode=mode, header=header)
+            if long_path is not None:
+                long = out["long"]
+                lt = pd.DataFrame({"data_ix": ix[host(long["row"]).astype(np.int64)]})
+                for name, kind in long_columns:
+                    lt[name] = host(long[name]).astype(kind)
+                with_annotation(lt).to_csv(paths[1][1], index=False, mode=mode, header=header)
             header = False
             written += len(table)
         if finish is not None:
             finish()  # a timed-out persistent launch fails the run, not the table
     except BaseException:
-        if os.path.isfile(tmp_path):
-            os.remove(tmp_path)
+        for _, tmp_path in paths:
+            if os.path.isfile(tmp_path):
+                os.remove(tmp_path)
         raise
-    if os.path.isfile(tmp_path):  # (an empty dataset writes no table, as encode.py)
-        rename_existing_file(save_path)
-        os.replace(tmp_path, save_path)
+    for path, tmp_path in paths:
+        if os.path.isfile(tmp_path):  # (an empty dataset writes no table, as encode.py)
+            rename_existing_file(path)
+            os.replace(tmp_path, path)
     return written
 
 
