@@ -515,6 +515,72 @@ int abcd_featurize_packed(const float* wave, const long long* seg_off, const lon
                           size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Log-spectra back to audio: the inverse of the featuriser above, phase
+ * retrieval by Griffin-Lim (Griffin & Lim 1984; momentum form: Perraudin,
+ * Balazs & Sondergaard 2013) run entirely on the device.  The reference has
+ * no such path.
+ *
+ * logamp: packed L x F log-amplitudes (row stride ld >= F = n_fft/2 + 1), what
+ * abcd_featurize_packed writes and abcd_decoder_generate returns; phase0: L
+ * rows of F radians (row stride ldp >= F), the initial phase; batch_sizes:
+ * HOST.  Magnitudes A = max(exp(logamp * norm) - eps, 0).  torch.stft /
+ * torch.istft semantics with center = 1: segment b (packed position b, T_b
+ * frames) gets S_b = hop (T_b - 1) samples,
+ *
+ *   C = A exp(i phase0);  R_prev = 0
+ *   n_iter times:  y = istft(C);  R = stft(y);  t = R - momentum / (1 + momentum) R_prev;
+ *                  R_prev = R;  C = A t / (|t| + 1e-16)
+ *   wave[b] = istft(C);  residual[b] = || |stft(wave[b])| - A ||_F / ||A||_F
+ *
+ * istft: the inverse real DFT of each frame (imaginary parts of the DC and,
+ * for even n_fft, Nyquist bins ignored) times the window, overlap-added and
+ * divided by the overlap-added squared window (samples where that is < 1e-11
+ * become 0), n_fft/2 samples trimmed at the front, S_b kept.  stft: the signal
+ * reflect-padded by n_fft/2 in front and n_fft - n_fft/2 behind and framed as
+ * abcd_featurize_packed frames it: T_b frames (for odd n_fft the last frame
+ * reads one reflected sample more than torch.stft's centre padding holds, which
+ * would drop that frame).  n_iter = 0 is the plain inverse STFT of a spectrum
+ * with known phase; momentum = 0 is classic Griffin-Lim, 0.99 the fast form.
+ *
+ * The padding needs S_b > n_fft - n_fft/2: abcd_griffin_lim_samples returns 0
+ * for fewer frames than that (or center = 0), and such a segment gets a zero
+ * row and residual NaN.  Row b of wave (B rows, stride ldw >= the longest
+ * S_b) holds segment b's samples followed by zeros.  residual: B floats or
+ * NULL (it costs one more STFT).
+ *
+ * One launch: one 1024-thread workgroup per segment runs the whole iteration
+ * loop with nothing but workgroup barriers between the phases; no atomics, no
+ * workgroup waits for another.  The reflect-padded signal stays in LDS for the
+ * whole loop wherever it fits beside the window and the twiddle table
+ * (S + 4 n_fft floats + 256 bytes <= 160 KiB for the longest segment's S: the
+ * switch is computed per call, e.g. at n_fft 256, hop 128 up to T = 312), else
+ * in ws; the phasors (scaled by A) and R_prev (T x F complex each per segment)
+ * live in ws.  ABCD_GL_LDS=0 in the environment forces the signal into ws
+ * (ABCD_GL_WAVES=8 / 4: fewer than 16 waves per workgroup, for A/B timing; the
+ * dispatch name then ends in " waves 8").  The DFTs are direct, fp32, with an
+ * n_fft-entry twiddle table built in double (any n_fft >= 2, odd included);
+ * every sum has a fixed order (the overlap-add is a gather per output sample in
+ * frame order), so two calls agree bit for bit and a segment's result does not
+ * depend on the rest of the batch.
+ * abcd_dispatch_name(16) names the form that ran ("griffin_lim<lds,dft> grid 3
+ * lds 106240" / "griffin_lim<global,dft> grid 2 lds 3328": the signal's home,
+ * the DFT form, workgroups, LDS bytes); abcd_timing_read_kernel id 16.
+ * ABCD_EINVAL (checked before any launch, nothing is written): center = 0
+ * (a Hann window violates the overlap-add condition at the edges there),
+ * ld or ldp < F, ldw too short, a NULL window / logamp / phase0 / wave, a
+ * missing or short workspace, n_iter < 0, momentum outside [0, 1), norm = 0,
+ * T > 16383, a batch_sizes abcd_segment_losses rejects, an n_fft whose tables
+ * alone exceed the LDS.
+ * abcd_griffin_lim_workspace_bytes is 0 for unsupported sizes.
+ * ---------------------------------------------------------------------- */
+int abcd_griffin_lim_samples(int frames, int n_fft, int hop, int center); /* S_b, 0 if too short */
+size_t abcd_griffin_lim_workspace_bytes(int B, int T, int n_fft, int hop);
+int abcd_griffin_lim(const float* logamp, int ld, const int64_t* batch_sizes, int T, int L, int B, int n_fft, int hop,
+                     int center, const float* window, float eps, float norm, const float* phase0, int ldp,
+                     int n_iter, float momentum, float* wave, int ldw, float* residual /* B or NULL */, void* ws,
+                     size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Optimiser: torch.nn.utils.clip_grad_norm_ + torch.optim.SGD
  * (learning.py:161-163, 256) over one flat fp32 parameter/gradient buffer.
  * ---------------------------------------------------------------------- */
@@ -573,7 +639,9 @@ int abcd_timing_read_kernel(int kid, double* out);
 /* which kernel the last launch of a role ran (same ids as abcd_timing_read_kernel,
  * 5 / 6 the sampler head forward / backward, 7 the encoder's layer-0 weight
  * gradients; e.g. "dec_bwd_sk<9,16,16,LSTM> grid 256" or "per-step ..."), and how many
- * launches of the role since abcd_dispatch_reset; host-side bookkeeping only */
+ * launches of the role since abcd_dispatch_reset; host-side bookkeeping only.
+ * An id outside the table reads as "" / -1; so does 15, which stays unassigned
+ * (it was the first id out of range before the table grew, and callers probe it). */
 const char* abcd_dispatch_name(int kid);
 long abcd_dispatch_count(int kid);
 void abcd_dispatch_reset(void);

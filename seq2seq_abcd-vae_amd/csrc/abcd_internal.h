@@ -236,8 +236,11 @@ enum TimedKernel {
   // 8 .. 10: the generation cut's launches (abcd_generate.hip, live timing only)
   TK_SEG_LOSSES = 11, TK_KL_ROWS = 12,  // abcd_score.hip: live timing and dispatch records
   TK_PAIR_NLL = 13, TK_PAIR_POST = 14,  // abcd_pairwise.hip: live timing and dispatch records
-  TK_N = 15
+  TK_UNASSIGNED = 15,   // never assigned: reads as out of range, which callers written against 15 ids rely on
+  TK_GRIFFIN_LIM = 16,  // abcd_vocoder.hip: live timing and dispatch record (which form ran)
+  TK_N = 17
 };
+inline bool tk_valid(int kid) { return kid >= 0 && kid < TK_N && kid != TK_UNASSIGNED; }
 bool timing_on();
 void timing_mark(hipStream_t s, int kid);
 // records which kernel (template instance) a role's last launch ran, so the

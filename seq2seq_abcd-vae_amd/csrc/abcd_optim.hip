@@ -188,7 +188,7 @@ namespace abcd {
 static char g_dispatch[TK_N][128];
 static long g_dispatch_n[TK_N];
 void note_dispatch(int kid, const char* fmt, ...) {
-  if (kid < 0 || kid >= TK_N) return;
+  if (!tk_valid(kid)) return;
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_dispatch[kid], sizeof(g_dispatch[kid]), fmt, ap);
@@ -198,9 +198,9 @@ void note_dispatch(int kid, const char* fmt, ...) {
 }  // namespace abcd
 
 extern "C" const char* abcd_dispatch_name(int kid) {
-  return (kid < 0 || kid >= abcd::TK_N) ? "" : abcd::g_dispatch[kid];
+  return abcd::tk_valid(kid) ? abcd::g_dispatch[kid] : "";
 }
-extern "C" long abcd_dispatch_count(int kid) { return (kid < 0 || kid >= abcd::TK_N) ? -1 : abcd::g_dispatch_n[kid]; }
+extern "C" long abcd_dispatch_count(int kid) { return abcd::tk_valid(kid) ? abcd::g_dispatch_n[kid] : -1; }
 extern "C" void abcd_dispatch_reset(void) {
   for (int k = 0; k < abcd::TK_N; ++k) {
     abcd::g_dispatch[k][0] = 0;

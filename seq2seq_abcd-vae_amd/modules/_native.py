@@ -159,6 +159,11 @@ _SIGS = {
     "abcd_featurize_packed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float,
                                       c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                       c_void_p]),
+    "abcd_griffin_lim_samples": (c_int, [c_int, c_int, c_int, c_int]),
+    "abcd_griffin_lim_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "abcd_griffin_lim": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float,
+                                 c_float, c_void_p, c_int, c_int, c_float, c_void_p, c_int, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
     "abcd_optim_workspace_bytes": (c_size_t, [c_long]),
     "abcd_grad_norm": (c_int, [c_void_p, c_long, c_void_p, c_void_p, c_size_t, c_void_p]),
     "abcd_clip_sgd": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_int, c_void_p,
@@ -235,7 +240,8 @@ def source_hash():
     import hashlib
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     names = ["abcd_gemm.hip", "abcd_rnn.hip", "abcd_persist.hip", "abcd_sampler.hip", "abcd_optim.hip",
-             "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_common.h", "abcd_internal.h",
+             "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_vocoder.hip", "abcd_common.h",
+             "abcd_internal.h",
              "abcd_persist.h", "abcd_special.h", "abcd_x6.h", "../../include/abcd_hip.h"]
     h = hashlib.sha256()
     for n in sorted(names):
@@ -341,6 +347,7 @@ def workspace(nbytes, device):
 ENC_FWD, ENC_BWD, DEC_FWD, DEC_BWD, SAMP_FWD, SAMP_BWD, ENC_WGRAD = 1, 2, 3, 4, 5, 6, 7
 SEG_LOSSES, KL_ROWS = 11, 12  # abcd_segment_losses / abcd_sampler_kl_rows (timing and dispatch ids)
 PAIR_NLL, PAIR_POST = 13, 14  # abcd_pairwise_nll / abcd_pair_posterior (timing and dispatch ids)
+GRIFFIN_LIM = 16  # abcd_griffin_lim (timing and dispatch id: the name says which form ran); 15 stays unassigned
 
 
 def dispatch():
@@ -350,7 +357,8 @@ def dispatch():
             for r, k in (("enc_fwd", ENC_FWD), ("enc_bwd", ENC_BWD), ("dec_fwd", DEC_FWD), ("dec_bwd", DEC_BWD),
                                 ("samp_fwd", SAMP_FWD), ("samp_bwd", SAMP_BWD), ("enc_wgrad", ENC_WGRAD),
                                 ("seg_losses", SEG_LOSSES), ("kl_rows", KL_ROWS),
-                                ("pair_nll", PAIR_NLL), ("pair_post", PAIR_POST))}
+                                ("pair_nll", PAIR_NLL), ("pair_post", PAIR_POST),
+                                ("griffin_lim", GRIFFIN_LIM))}
 
 
 def ptr_array(tensors):

@@ -212,6 +212,54 @@ class DeviceFeaturizer(object):
         return out, batch_sizes, is_off
 
 
+class DeviceVocoder(object):
+    """The mirror of DeviceFeaturizer: packed log-amplitude frames (what it
+    writes, what ``RNN_Variational_Decoder.generate`` returns) back to audio by
+    Griffin-Lim phase retrieval on the GPU (libabcd_hip: abcd_griffin_lim, one
+    launch for the whole batch and every iteration).  The reference has no
+    inverse path.  Takes a PackedSequence or ``(data L x F, batch_sizes)``;
+    returns ``(waves B x S_max, n_samples int64 B, residual B)`` in packed row
+    order: row b holds ``n_samples[b] = hop * (T_b - 1)`` samples on the scale of
+    the featurised audio, then zeros; ``residual[b]`` is the relative spectral
+    error ``|| |STFT(wave)| - A || / ||A||`` (NaN when not asked for).  A
+    segment too short for the reflect padding has ``n_samples = 0``, a zero row
+    and a NaN residual."""
+
+    def __init__(self, frame_length, step_size, window="hann_window", centering=True, eps=2 ** (-15),
+                 normalizer=1.0, device="cuda"):
+        self.n_fft, self.hop, self.center = int(frame_length), int(step_size), bool(centering)
+        if not self.center:
+            raise ValueError("DeviceVocoder: centering=False is not supported (a Hann window violates the overlap-add "
+                             "condition at the edges there; torch.istft refuses it too)")
+        self.eps, self.norm = float(eps), float(normalizer)
+        self.device = torch.device(device)
+        self.window = getattr(torch, window)(self.n_fft).to(self.device, torch.float32).contiguous()
+
+    def num_samples(self, frames):
+        from . import _native as N
+        return int(N.lib().abcd_griffin_lim_samples(int(frames), self.n_fft, self.hop, 1))
+
+    def __call__(self, packed, n_iter=32, momentum=0.99, phase=None, seed=None, residual=True):
+        from . import ops
+        data, batch_sizes = (packed.data, packed.batch_sizes) if hasattr(packed, "batch_sizes") else packed
+        data = data.to(self.device)
+        bs = batch_sizes.to("cpu", torch.int64)
+        B = int(bs[0])
+        lengths = [int((bs > b).sum()) for b in range(B)]
+        if phase is None:  # U(-pi, pi) on the device; the same seed gives the same bits
+            g = torch.Generator(device=self.device)
+            if seed is None:
+                g.seed()
+            else:
+                g.manual_seed(int(seed))
+            phase = (torch.rand(data.shape, generator=g, device=self.device) * 2.0 - 1.0) * np.pi
+        with torch.no_grad():
+            waves, res = ops.griffin_lim(data, bs, self.window, phase.to(self.device), self.hop, self.eps, self.norm,
+                                         int(n_iter), float(momentum), bool(residual))
+        n_samples = torch.tensor([self.num_samples(n) for n in lengths], dtype=torch.int64)
+        return waves, n_samples, res
+
+
 class DataLoader(object):
     """data_utils.py:150-185: yields (PackedSequence, packed is_offset, speakers, ixs).
 

@@ -25,10 +25,11 @@ operator                   replaces (reference)                            C ent
 ``abcd::sampler_kl_rows``  (none: per-row part of ``kl_divergence``)       ``abcd_sampler_kl_rows``
 ``abcd::pairwise_nll``     (none: every segment x every prototype)         ``abcd_pairwise_nll``
 ``abcd::pair_posterior``   (none: responsibilities, evidence, argmax)      ``abcd_pair_posterior``
+``abcd::griffin_lim``      (none: log-spectra back to audio)               ``abcd_griffin_lim``
 =========================  ==============================================  =========================================
 
-The last four are forward-only (scoring): they have no autograd formula and
-raise when an input requires grad outside ``torch.no_grad()``.
+The last five are forward-only (scoring, synthesis): they have no autograd
+formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
 configuration travels as an ``int[]`` in the C struct's field order, the
@@ -754,9 +755,61 @@ def _(pair_em, pair_off, log_weight):
 _forward_only(pair_posterior, "pair_posterior")
 
 
+# ----------------------------------------------------------------------------
+# log-spectra back to audio (forward-only)
+# ----------------------------------------------------------------------------
+@torch.library.custom_op("abcd::griffin_lim", mutates_args=())
+def griffin_lim(logamp: Tensor, batch_sizes: Tensor, window: Tensor, phase0: Tensor, hop: int, eps: float,
+                norm: float, n_iter: int, momentum: float, want_residual: bool) -> List[Tensor]:
+    """-> [waves (B x S_max), residual (B)]: Griffin-Lim phase retrieval of the
+    packed log-amplitude frames (L x F, F = n_fft / 2 + 1, n_fft = the
+    window's length; row-strided views pass without a copy) from the initial
+    phase phase0 (L x F radians), torch.stft semantics with center=True.  Row b
+    is the segment at packed position b, hop * (T_b - 1) samples followed by
+    zeros; a segment too short for the reflect padding gets a zero row and a
+    NaN residual.  residual is NaN everywhere when not asked for."""
+    for t in (logamp, window, phase0):
+        N.require_gpu(t)
+    n_fft = int(window.numel())
+    F = n_fft // 2 + 1
+    if logamp.dim() != 2 or logamp.shape[1] != F or tuple(phase0.shape) != tuple(logamp.shape):
+        raise ValueError(f"griffin_lim: logamp and phase0 must be L x {F}, got {tuple(logamp.shape)} and "
+                         f"{tuple(phase0.shape)}")
+    dev = logamp.device
+    (x, ld), (ph, ldp) = _rows(logamp.float()), _rows(phase0.float())
+    win = window.float().contiguous()
+    L_ = N.lib()
+    pk, bs = _packed(x, batch_sizes, F)
+    smax = int(L_.abcd_griffin_lim_samples(pk.T, n_fft, int(hop), 1))
+    nbytes = L_.abcd_griffin_lim_workspace_bytes(pk.B, pk.T, n_fft, int(hop))
+    if nbytes == 0:
+        raise N.HipError("griffin_lim: unsupported shape (more than 16383 steps, or an n_fft whose tables exceed the LDS)")
+    ws = N.workspace(nbytes, dev)
+    waves = torch.empty(pk.B, max(smax, 1), device=dev)
+    residual = torch.full((pk.B,), float("nan"), device=dev)
+    N.check(L_.abcd_griffin_lim(N.ptr(x), ld, bs.data_ptr(), pk.T, pk.L, pk.B, n_fft, int(hop), 1, N.ptr(win),
+                                float(eps), float(norm), N.ptr(ph), ldp, int(n_iter), float(momentum), N.ptr(waves),
+                                waves.shape[1], N.ptr(residual) if want_residual else None, N.ptr(ws), ws.numel(),
+                                N.stream()), "griffin lim")
+    return [waves[:, :smax], residual]
+
+
+@griffin_lim.register_fake
+def _(logamp, batch_sizes, window, phase0, hop, eps, norm, n_iter, momentum, want_residual):
+    B = int(batch_sizes[0]) if batch_sizes.numel() else 0
+    n_fft = int(window.numel())
+    smax = max(int(hop) * (int(batch_sizes.numel()) - 1), 0)
+    if smax <= n_fft - n_fft // 2:  # abcd_griffin_lim_samples: too short for the reflect padding
+        smax = 0
+    return [logamp.new_empty(B, smax, dtype=torch.float32), logamp.new_empty(B, dtype=torch.float32)]
+
+
+_forward_only(griffin_lim, "griffin_lim")
+
+
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
-       "pairwise_nll", "pair_posterior")
+       "pairwise_nll", "pair_posterior", "griffin_lim")
 
 
 def registered() -> Sequence[str]:
