@@ -496,6 +496,66 @@ int abcd_pair_posterior(const float* pair_em, const float* pair_off, long ld_pai
                         long ld_resp, void* stream);
 
 /* ------------------------------------------------------------------------
+ * A hidden Markov model over the category sequence of a recording: the K
+ * categories are the states, score[n ld_score + k] the log-likelihood of
+ * segment n under category k up to a per-row constant (the callers take each
+ * row's maximum off, ops.chain_scores), log_trans[i ld_trans + j] = log p(z_t+1
+ * = j | z_t = i) and log_init[k] log-probabilities (-inf: a structural zero).
+ * Sequence s owns rows seq_off[s] .. seq_off[s + 1] - 1 in time order; seq_off
+ * is a HOST array of S + 1 entries, validated on the host and copied to the
+ * workspace through the pinned offset ring, 16384 entries per slot (a longer
+ * table takes several slots); the call does no host synchronisation.
+ *
+ * abcd_chain_posterior, per sequence of rows 0 .. T - 1:
+ *   alpha_0 = log_init + score_0,
+ *   alpha_t+1[j] = score_t+1[j] + logsumexp_i(alpha_t[i] + log_trans[i,j]);
+ *   log_evidence[s] = logsumexp_k alpha_T-1[k];
+ *   beta_T-1 = 0, beta_t[i] = logsumexp_j(log_trans[i,j] + score_t+1[j] + beta_t+1[j]);
+ *   gamma[n ld_gamma + k] = exp(alpha_t[k] + beta_t[k] - log_evidence) (rows sum to 1);
+ *   xi_t[i,j] = exp(alpha_t[i] + log_trans[i,j] + score_t+1[j] + beta_t+1[j] - log_evidence);
+ *   trans_counts[i K + j] = sum_s sum_t xi_t[i,j];  init_counts[k] = sum_s gamma_0[k];
+ *   path: delta_0 = alpha_0, delta_t+1[j] = score_t+1[j] + max_i(delta_t[i] + log_trans[i,j]),
+ *   the final state and every back-pointer the LOWEST index attaining the
+ *   maximum; path_score[s] = the path's log joint log_init[p_0] + score_0[p_0] +
+ *   sum_t log_trans[p_t, p_t+1] + score_t+1[p_t+1].
+ * Every output may be NULL.  Groups (the `want` of the workspace query): 1
+ * log_evidence, 2 gamma, 4 path / path_score, 8 trans_counts / init_counts; a
+ * Viterbi-only call stores no alphas.  All of it runs in the log domain: every
+ * vector is renormalised to a maximum of 0 after each step in fp32, and what
+ * was taken off (the evidence), the counts and path_score accumulate in fp64.
+ * A score entry that is NaN or +inf counts as -inf.  A sequence whose forward
+ * mass vanishes (an all-excluded row, zeros that leave no path) gets
+ * log_evidence = -inf, gamma = 0, path = -1, path_score = -inf and adds nothing
+ * to the counts; a zero-length sequence gets log_evidence = 0 and nothing else;
+ * a length-1 sequence adds to init_counts only.
+ *
+ * One workgroup owns a sequence for all of its time loops; workgroup g of G
+ * takes sequences g, g + G, ...  abcd_chain_plan (a pure function) reports G
+ * for an S and whether a K runs resident (log_trans in LDS for the whole
+ * launch, K <= 128) or streaming (log_trans read from global memory every
+ * step, K <= 1024).  The counts are summed by a launch of their own from the
+ * alpha and score + beta rows the backward pass stores (resident: workgroup g
+ * sums its sequences into a slab of fp64 partials in the workspace, and a last
+ * small launch adds the slabs in workgroup order; streaming: the K x K entries
+ * are tiled over the workgroups and each walks every sequence in order): no
+ * atomics, no device-global word, no workgroup waits for another, and two
+ * calls on the same inputs agree bit for bit.  No timing or dispatch id is
+ * assigned.
+ * abcd_chain_workspace_bytes is 0 for K < 1, K > 1024, N < 0, S < 0, N K >=
+ * 2^31 or a want outside 0 .. 15.  ABCD_EINVAL (checked before any launch,
+ * nothing is written): those shapes; seq_off NULL, not non-decreasing,
+ * seq_off[0] != 0 or seq_off[S] != N; a stride below K; score, log_trans or
+ * log_init NULL while an output is requested; a missing or short workspace.
+ * With every output NULL a valid call returns 0 without a device.
+ * ---------------------------------------------------------------------- */
+size_t abcd_chain_workspace_bytes(long N, int S, int K, int want);
+int abcd_chain_plan(int K, int S, int* resident, int* workgroups);
+int abcd_chain_posterior(const float* score, long ld_score, long N, int K, const int64_t* seq_off, int S,
+                         const float* log_trans, long ld_trans, const float* log_init, double* log_evidence,
+                         float* gamma, long ld_gamma, int32_t* path, double* path_score, double* trans_counts,
+                         double* init_counts, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

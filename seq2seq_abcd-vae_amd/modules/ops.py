@@ -26,9 +26,10 @@ operator                   replaces (reference)                            C ent
 ``abcd::pairwise_nll``     (none: every segment x every prototype)         ``abcd_pairwise_nll``
 ``abcd::pair_posterior``   (none: responsibilities, evidence, argmax)      ``abcd_pair_posterior``
 ``abcd::griffin_lim``      (none: log-spectra back to audio)               ``abcd_griffin_lim``
+``abcd::chain_posterior``  (none: an HMM over category sequences)          ``abcd_chain_posterior``
 =========================  ==============================================  =========================================
 
-The last five are forward-only (scoring, synthesis): they have no autograd
+The last six are forward-only (scoring, synthesis): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -756,6 +757,107 @@ _forward_only(pair_posterior, "pair_posterior")
 
 
 # ----------------------------------------------------------------------------
+# a hidden Markov model over category sequences (forward-only)
+# ----------------------------------------------------------------------------
+CHAIN_EVIDENCE, CHAIN_GAMMA, CHAIN_PATH, CHAIN_COUNTS = 1, 2, 4, 8  # the groups of `want` (abcd_hip.h)
+CHAIN_ALL = 15
+
+
+def chain_plan(K, S):
+    """(resident, workgroups) of abcd_chain_plan: whether K runs with log_trans
+    resident in LDS, and how many workgroups S sequences get."""
+    res, wg = N.c_int(0), N.c_int(0)
+    N.check(N.lib().abcd_chain_plan(int(K), int(S), res, wg), "chain plan")
+    return bool(res.value), int(wg.value)
+
+
+def chain_scores(pair_em: Tensor, pair_off: Optional[Tensor], log_weight: Optional[Tensor] = None):
+    """-> (score B x K fp32, row_offset B fp64): s = log_weight - pair_em -
+    pair_off formed in float64 on the device (the NLLs are ~1e5 with gaps of
+    order 1, as in pair_posterior) with each row's maximum taken off; s =
+    score + row_offset[:, None].  NaN and +inf NLLs become -inf scores; a row
+    with nothing left keeps offset 0."""
+    s = -pair_em.double()
+    if pair_off is not None:
+        s = s - pair_off.double()
+    if log_weight is not None:
+        s = s + log_weight.double()[None, :]
+    ninf = torch.full_like(s, float("-inf"))
+    s = torch.where((s > float("-inf")) & (s < float("inf")), s, ninf)
+    m = s.max(dim=1).values
+    m = torch.where(m > float("-inf"), m, torch.zeros_like(m))
+    return (s - m[:, None]).float(), m
+
+
+@torch.library.custom_op("abcd::chain_posterior", mutates_args=())
+def chain_posterior(score: Tensor, seq_off: Tensor, log_trans: Tensor, log_init: Tensor, want: int) -> List[Tensor]:
+    """-> [log_evidence (S, fp64), gamma (N x K), path (N, int32), path_score
+    (S, fp64), trans_counts (K x K, fp64), init_counts (K, fp64)] of the hidden
+    Markov model with emission scores score (N x K, row-strided views pass
+    without a copy), sequences seq_off (S + 1 row offsets, a HOST int64 tensor),
+    log_trans (K x K) and log_init (K): abcd_chain_posterior.  want is a sum of
+    CHAIN_EVIDENCE, CHAIN_GAMMA, CHAIN_PATH and CHAIN_COUNTS; the outputs of a
+    group that is not asked for are empty tensors."""
+    for t in (score, log_trans, log_init):
+        N.require_gpu(t)
+    want = int(want)
+    if score.dim() != 2 or score.shape[1] < 1:
+        raise ValueError(f"chain_posterior: score must be N x K, got {tuple(score.shape)}")
+    n, K = (int(v) for v in score.shape)
+    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
+        raise ValueError(f"chain_posterior: log_trans must be {(K, K)} and log_init hold {K} entries")
+    if want < 0 or want > CHAIN_ALL:
+        raise ValueError(f"chain_posterior: want must lie in 0 .. {CHAIN_ALL}")
+    so = seq_off
+    if so.dtype != torch.int64 or so.device.type != "cpu":
+        so = so.to("cpu", torch.int64)
+    so = so.contiguous()
+    S = int(so.numel()) - 1
+    if S < 0:
+        raise ValueError("chain_posterior: seq_off must hold S + 1 offsets")
+    dev = score.device
+    (sc, lds), (lt, ldt) = _rows(score.float()), _rows(log_trans.float())
+    li = log_init.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_chain_workspace_bytes(n, S, K, want)
+    if nbytes == 0:
+        raise N.HipError("chain_posterior: unsupported shape (K > 1024 or N * K >= 2^31)")
+    ws = N.workspace(nbytes, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    ev = torch.empty(S if want & CHAIN_EVIDENCE else 0, **f64)
+    gamma = torch.empty(n if want & CHAIN_GAMMA else 0, K, device=dev)
+    path = torch.empty(n if want & CHAIN_PATH else 0, dtype=torch.int32, device=dev)
+    ps = torch.zeros(S if want & CHAIN_PATH else 0, **f64)  # a zero-length sequence's entry is not written
+    tc = torch.empty((K, K) if want & CHAIN_COUNTS else (0, K), **f64)
+    ic = torch.empty(K if want & CHAIN_COUNTS else 0, **f64)
+
+    def p(t, bit):
+        return N.ptr(t) if want & bit else None
+    N.check(L_.abcd_chain_posterior(N.ptr(sc), lds, n, K, so.data_ptr(), S, N.ptr(lt), ldt, N.ptr(li),
+                                    p(ev, CHAIN_EVIDENCE), p(gamma, CHAIN_GAMMA), K, p(path, CHAIN_PATH),
+                                    p(ps, CHAIN_PATH), p(tc, CHAIN_COUNTS), p(ic, CHAIN_COUNTS), N.ptr(ws),
+                                    ws.numel(), N.stream()), "chain posterior")
+    return [ev, gamma, path, ps, tc, ic]
+
+
+@chain_posterior.register_fake
+def _chain_posterior_fake(score, seq_off, log_trans, log_init, want):
+    n, K = score.shape
+    S = int(seq_off.numel()) - 1
+    want = int(want)
+    e = score.new_empty
+    return [e(S if want & CHAIN_EVIDENCE else 0, dtype=torch.float64),
+            e(n if want & CHAIN_GAMMA else 0, K, dtype=torch.float32),
+            e(n if want & CHAIN_PATH else 0, dtype=torch.int32),
+            e(S if want & CHAIN_PATH else 0, dtype=torch.float64),
+            e((K, K) if want & CHAIN_COUNTS else (0, K), dtype=torch.float64),
+            e(K if want & CHAIN_COUNTS else 0, dtype=torch.float64)]
+
+
+_forward_only(chain_posterior, "chain_posterior")
+
+
+# ----------------------------------------------------------------------------
 # log-spectra back to audio (forward-only)
 # ----------------------------------------------------------------------------
 @torch.library.custom_op("abcd::griffin_lim", mutates_args=())
@@ -809,7 +911,7 @@ _forward_only(griffin_lim, "griffin_lim")
 
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
-       "pairwise_nll", "pair_posterior", "griffin_lim")
+       "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior")
 
 
 def registered() -> Sequence[str]:
