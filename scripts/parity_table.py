@@ -4,10 +4,12 @@
     ABCD_PARITY_DUMP=<dir> python -m pytest -m gpu tests
     python scripts/parity_table.py <dir>
 
-tests/test_gpu_edges.py, test_gpu_fullshape.py and test_gpu_prod.py write the
-errors they observed (the HIP path against the float64 / fp32 oracle or the
-reference's fixtures) into <dir> when ABCD_PARITY_DUMP is set; this puts them
-into one table next to the tolerances derived from them.
+tests/test_gpu_edges.py, test_gpu_fullshape.py, test_gpu_prod.py,
+test_gpu_sampler_widths.py and test_gpu_philox.py write the errors they
+observed (the HIP path against the float64 / fp32 oracle or the reference's
+fixtures) into <dir> when ABCD_PARITY_DUMP is set; this puts them into one
+table next to the tolerances derived from them.  A section <dir> holds no
+figures for (a run of some of the files) keeps what the table has.
 """
 import glob
 import json
@@ -27,13 +29,26 @@ def main(src):
     import test_gpu_edges as TE
     import test_gpu_fullshape as TF
     import test_gpu_prod as TP
-    edges, full, prod = {}, {}, {}
-    worst_ratio = {}
+    import test_gpu_sampler_widths as TS
+    edges, full, prod, samp, philox = {}, {}, {}, {}, {}
+    worst_ratio, samp_ratio = {}, {}
     for path in sorted(glob.glob(os.path.join(src, "*.json"))):
         name = os.path.basename(path)[:-5]
         with open(path) as f:
             d = json.load(f)
-        if name.startswith("fullshape-"):
+        if name.startswith("samp-"):
+            rows = {}
+            for r in d:
+                k = r["tensor"]
+                rows[k] = [sig(r["e32_rel"]), sig(r["e_hip_rel"]), sig(r["e32_blk"]), sig(r["e_hip_blk"]), r["R"]]
+                for a, b in ((r["e_hip_rel"], r["e32_rel"]), (r["e_hip_blk"], r["e32_blk"])):
+                    if r["R"] is not None and a > TS.R_DEFAULT * b + 1e-7:  # past the default bound
+                        key = f"{name[len('samp-'):]}: {k}"
+                        samp_ratio[key] = max(samp_ratio.get(key, 0.0), sig(a / max(b, 1e-30)))
+            samp[name[len("samp-"):]] = rows
+        elif name.startswith("philox-"):
+            philox[name[len("philox-"):]] = {k: (sig(v) if isinstance(v, float) else v) for k, v in d[0].items()}
+        elif name.startswith("fullshape-"):
             full[name[len("fullshape-"):]] = dict(
                 clip=sig(d["clip"]), worst={m: sig(x) for m, x in d["worst"].items()},
                 tensors={k: {m: sig(x) for m, x in v.items()} for k, v in d["tensors"].items()})
@@ -85,8 +100,32 @@ def main(src):
             "worst": max(c["worst"] for c in prod.values()) if prod else None,
             "cases": prod,
         },
+        "sampler_widths": {
+            "file": "tests/test_gpu_sampler_widths.py, tests/test_gpu_philox.py",
+            "reference": "the float64 oracle on the un-padded model (tests/sampler_cases.py)",
+            "columns": ["e32_rel", "e_hip_rel", "e32_blk", "e_hip_blk", "R"],
+            "bound": "e_hip <= R * e32 + 1e-7, and e_hip <= %g whatever R; R null: recorded only, under the "
+                     "hard bound alone (in-kernel Gumbel noise: the device's fast log)" % TS.HARD,
+            "R_default": TS.R_DEFAULT, "R_case_tensor": {f"{c}: {k}": r for (c, k), r in TS.R_TENSOR.items()},
+            "worst_ratio_past_R_default": samp_ratio,
+            "R_note": TS.R_NOTE,
+            "worst_e_hip": {m: max(r[i] for rows in samp.values() for r in rows.values())
+                            for m, i in (("rel", 1), ("blk", 3))} if samp else {},
+            "worst_e_hip_per_case": {c: {m: max(r[i] for r in rows.values()) for m, i in (("rel", 1), ("blk", 3))}
+                                     for c, rows in samp.items() if rows},
+            "fill_normal": philox,
+            "cases": samp,
+        },
     }
     out = os.path.join(REPO, "profiles", "parity_errors.json")
+    # a section <dir> has no figures for keeps what the file holds
+    if os.path.isfile(out):
+        with open(out) as f:
+            old = json.load(f)
+        for sec, got in (("edge_cases", edges), ("full_shape", full), ("prod_fixtures", prod),
+                         ("sampler_widths", samp or philox)):
+            if not got and sec in old:
+                table[sec] = old[sec]
     text = json.dumps(table, indent=1)
     # one line per tensor: collapse the arrays of numbers
     text = re.sub(r"\[\s+([^\[\]{}]*?)\s+\]", lambda m: "[" + re.sub(r"\s+", " ", m.group(1)) + "]", text)

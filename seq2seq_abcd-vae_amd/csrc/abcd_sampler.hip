@@ -186,10 +186,13 @@ __global__ void kl_rows_bwd(const float* Q, const float* elog, const float* v, i
 }
 
 // d posterior_shape_logits (model.py:620-633 backward), one block; Qsum[k] =
-// sum_b Q(b, k) (global or block-shared)
+// sum_b Q(b, k) (global or block-shared).  K: the categories; the padding
+// entries K .. Kp - 1 of a zero-padded model's gradient are written as 0.
 DEV void prior_bwd_block(const float* p, const float* alpha, const float* tri, const double* kl_small,
-                         const float* Qsum, int K, int B, double N, float a0, float dkl, float* dpsl, double* sh) {
+                         const float* Qsum, int K, int Kp, int B, double N, float a0, float dkl, float* dpsl,
+                         double* sh) {
   const int tid = threadIdx.x, nt = blockDim.x;
+  for (int k = K + tid; k < Kp; k += nt) dpsl[k] = 0.f;
   const double s = dkl;
   const double r = (double)B / N;
   double sde = 0.0;
@@ -210,9 +213,10 @@ DEV void prior_bwd_block(const float* p, const float* alpha, const float* tri, c
   }
 }
 __global__ void kl_prior_bwd(const float* p, const float* alpha, const float* tri, const double* kl_small,
-                             const float* Qsum, int K, int B, double N, float a0, const float* dkl, float* dpsl) {
+                             const float* Qsum, int K, int Kp, int B, double N, float a0, const float* dkl,
+                             float* dpsl) {
   __shared__ double sh[16];
-  prior_bwd_block(p, alpha, tri, kl_small, Qsum, K, B, N, a0, *dkl, dpsl, sh);
+  prior_bwd_block(p, alpha, tri, kl_small, Qsum, K, Kp, B, N, a0, *dkl, dpsl, sh);
 }
 
 __global__ void tanh_bwd_inplace(float* dz, const float* z, long n) {
@@ -888,7 +892,7 @@ __global__ __launch_bounds__(NT) void samp_head_bwd(HeadBwdArgs a) {
   }
   __syncthreads();
   HSTAMP(6);
-  if (a.dpsl) prior_bwd_block(a.p, a.alpha, a.tri, a.kl_small, QcL, a.Kv, a.B, a.N, a.a0, s, a.dpsl, sh);
+  if (a.dpsl) prior_bwd_block(a.p, a.alpha, a.tri, a.kl_small, QcL, a.Kv, K, a.B, a.N, a.a0, s, a.dpsl, sh);
   HSTAMP(7);
 }
 
@@ -1219,7 +1223,7 @@ static int samp_kl_bwd(const abcd_sampler_cfg* c, const abcd_sampler_params* p, 
   if (d_psl) {  // forward products only: no wait on s beyond the caller's fork
     SideWork side(s, sw);
     ABCD_TRY((hipError_t)colsum(sw, w.Q, K, B, K, nullptr, w.Qsum, 0.f, w.scratch, w.scratch_floats));
-    kl_prior_bwd<<<1, 256, 0, sw>>>(w.p, w.alpha, w.tri, w.kl_small, w.Qsum, kvalid(c), B, N,
+    kl_prior_bwd<<<1, 256, 0, sw>>>(w.p, w.alpha, w.tri, w.kl_small, w.Qsum, kvalid(c), K, B, N,
                                     p->prior_concentration, d_kl, d_psl);
     ABCD_CHECK_LAUNCH();
   }
@@ -1479,6 +1483,30 @@ extern "C" int abcd_sampler_backward(const abcd_sampler_cfg* c, const abcd_sampl
 // its own column-sum row in LDS (no atomics, deterministic), summed over the
 // waves at the end.
 // rows of `ld` floats whose first K columns are the categories
+// K > 1024 (KPL 0): a row does not fit the lanes' registers; each wave makes
+// three passes over its rows.  Returns the wave's sum of row entropies.
+DEV double perplex_rows_loop(const float* logits, int B, int ld, int K, float* mine, int lane, int wv, int nw) {
+  double ent = 0.0;
+  for (int b = wv; b < B; b += nw) {
+    const float* l = logits + (long)b * ld;
+    float m = -INFINITY;
+    for (int k = lane; k < K; k += 64) m = fmaxf(m, l[k]);
+    m = wave_max(m);
+    float sm = 0.f;
+    for (int k = lane; k < K; k += 64) sm += __expf(l[k] - m);
+    sm = wave_sum(sm);
+    const float ls = __logf(sm), inv = 1.0f / sm;
+    float e = 0.f;
+    for (int k = lane; k < K; k += 64) {
+      const float z = l[k] - m;
+      const float qq = __expf(z) * inv;
+      e += -qq * (z - ls);
+      mine[k] += qq;
+    }
+    ent += wave_sum(e);
+  }
+  return ent;
+}
 template <int KPL>
 __global__ __launch_bounds__(1024) void perplex_kernel(const float* logits, int B, int ld, int K, const float* psl,
                                                        float* out) {
@@ -1492,8 +1520,10 @@ __global__ __launch_bounds__(1024) void perplex_kernel(const float* logits, int 
   // PR rows per wave in flight: every row's K values (KPL per lane) are loaded
   // before any is reduced, so the wave pays one memory latency per PR rows
   constexpr int PR = 4;
-  for (int b0 = wv * PR; b0 < B; b0 += nw * PR) {
-    float v[PR][KPL];
+  constexpr int KR = KPL ? KPL : 1;
+  if constexpr (KPL == 0) ent = perplex_rows_loop(logits, B, ld, K, mine, lane, wv, nw);
+  for (int b0 = wv * PR; KPL != 0 && b0 < B; b0 += nw * PR) {  // KPL 0: the looping form above instead
+    float v[PR][KR];
 #pragma unroll
     for (int rr = 0; rr < PR; ++rr)
 #pragma unroll
@@ -1625,6 +1655,7 @@ int perplexities_ld(const float* logits, int B, int ld, int K, const float* psl,
   else if (K <= 128) perplex_kernel<2><<<1, 64 * nw, lds, s>>>(logits, B, ld, K, psl, out);
   else if (K <= 256) perplex_kernel<4><<<1, 64 * nw, lds, s>>>(logits, B, ld, K, psl, out);
   else if (K <= 1024) perplex_kernel<16><<<1, 64 * nw, lds, s>>>(logits, B, ld, K, psl, out);
+  else if (lds <= 65536) perplex_kernel<0><<<1, 64 * nw, lds, s>>>(logits, B, ld, K, psl, out);  // K <= 16384
   else return ABCD_EINVAL;
   ABCD_CHECK_LAUNCH();
   return 0;
