@@ -556,6 +556,75 @@ int abcd_chain_posterior(const float* score, long ld_score, long N, int K, const
                          double* init_counts, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Segmentation: cutting an uncut recording into labelled segments.  With the
+ * prototypes of abcd_pairwise_nll (time-major rectangle, row t P + p, T_proto
+ * >= D steps) the log-likelihood of "frames s .. s + d - 1 are one segment of
+ * prototype p that ends after d frames" is
+ *   S[s,p,d] = log_weight[p] - E[s,p,d] - O[p,d],
+ *   E[s,p,d] = sum_{t < d} 0.5 sum_{f < F} (log 2pi + lv[t,p,f] + (x[s+t,f] - mu[t,p,f])^2 e^-lv[t,p,f]),
+ *   O[p,d]   = sum_{t < d-1} sp(o[t,p]) + sp(-o[d-1,p]),  sp(v) = max(v,0) + log1p(e^-|v|)
+ * (the BCE of the offset logits o against a target that is one on the last
+ * step: a duration model).  A frame's F columns are summed in fp32 in column
+ * order exactly as abcd_pairwise_nll sums them; everything across steps (E, O,
+ * the differences) is fp64 in step order.  A NULL log_weight counts as 0.
+ *
+ * abcd_span_scores: x is the recording, N frames with row stride ld_x >= F.
+ * The output is END-major: for e = s + d, 1 <= e <= N, 1 <= d <= min(D, e),
+ *   span_score[e ld_span + d - 1] = max_p S[e-d, p, d],
+ *   span_cat  [e ld_span + d - 1] = the lowest p attaining it,
+ * rows e = 0 .. N (N + 1 rows, ld_span >= D), so that the dynamic programme
+ * reads one contiguous row per step.  A p whose S is NaN or -inf (a NaN or
+ * +inf E, a NaN or -inf weight, a NaN O) is excluded; a span with nothing left,
+ * and every entry with d > e (row 0 among them), gets -inf and -1.  One
+ * workgroup owns 32 consecutive starts and walks the prototype tiles of 32
+ * itself, in order, so the maximum does not depend on scheduling: no atomics,
+ * no device-global word, no workgroup waits for another, two calls agree bit
+ * for bit, and S[s,p,d] is a function of frames s .. s + d - 1 alone (frames
+ * prepended to the recording shift the same bits).  Rows >= N of x, steps >= D
+ * of the rectangle and columns >= F are never read.  The workspace holds O
+ * (D P doubles).
+ * Limits: 1 <= D <= 16383, P >= 1, F >= 1, 0 <= N, (N + 1) D < 2^31; the
+ * workspace query returns 0 beyond them.  ABCD_EINVAL (checked before any
+ * launch, nothing is written): those shapes, T_proto < D, a stride below F,
+ * ld_span < D, x, proto_mu, proto_lv, proto_offset_logits, span_score or
+ * span_cat NULL while N > 0, a missing or short workspace.  N = 0 is valid and
+ * writes row 0 only (nothing when the outputs are NULL).
+ *
+ * abcd_span_viterbi: the semi-Markov dynamic programme over one recording,
+ *   V[0] = 0,
+ *   V[n] = max(V[n-1] + gap[n-1],
+ *              max_{d_min <= d <= min(D, n)} (V[n-d] + span_score[n ld_span + d - 1]) + seg_bonus)
+ * in fp64 with the additions made in exactly that order.  gap (N floats, may
+ * be NULL = -inf: the recording must be tiled by segments) is the per-frame
+ * log-likelihood of "no segment here", seg_bonus a per-segment log prior.  NaN
+ * candidates are excluded; the gap wins a tie against any segment, then the
+ * smallest d; V[n] = -inf when nothing is left.  One workgroup runs the whole
+ * loop and the backtrack in one launch (V in a ring of D doubles in LDS, one
+ * barrier per step) and writes the segments in time order: seg_onset,
+ * seg_length, seg_cat (span_cat of the chosen entry), seg_score (its
+ * span_score), each of N / d_min entries, n_segments of them valid;
+ * path_score = V[N].  An unreachable end (V[N] = -inf) gives path_score = -inf
+ * and n_segments = 0.  V_out (N + 1 doubles) may be NULL.  The workspace holds
+ * the N + 1 back-pointers.
+ * ABCD_EINVAL: d_min < 1 or d_min > D, the limits above, ld_span < D, a NULL
+ * among span_score, span_cat, path_score, n_segments and the four segment
+ * buffers while N > 0, a missing or short workspace.  N = 0 gives path_score =
+ * 0 and n_segments = 0 (each where not NULL) without reading anything.
+ *
+ * No timing or dispatch id is assigned to either entry point.
+ * ---------------------------------------------------------------------- */
+size_t abcd_span_scores_workspace_bytes(long N, int D, int P);
+int abcd_span_scores(const float* x, long ld_x, long N, int F, int P, int D, int T_proto, const float* proto_mu,
+                     long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                     const float* log_weight, double* span_score, int32_t* span_cat, long ld_span, void* ws,
+                     size_t ws_bytes, void* stream);
+size_t abcd_span_viterbi_workspace_bytes(long N, int D);
+int abcd_span_viterbi(const double* span_score, const int32_t* span_cat, long ld_span, long N, int D, int d_min,
+                      const float* gap, double seg_bonus, double* path_score, int32_t* n_segments,
+                      int32_t* seg_onset, int32_t* seg_length, int32_t* seg_cat, double* seg_score, double* V_out,
+                      void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

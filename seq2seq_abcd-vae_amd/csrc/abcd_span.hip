@@ -1,0 +1,425 @@
+// abcd_span.hip -- cut a recording into segments by the decoder.
+//
+// The prototypes of abcd_pairwise.hip do not depend on the data, and the
+// end-of-segment logits are a duration model, so the log-likelihood of "frames
+// s .. s + d - 1 are one segment of category p that ends at d" is defined for
+// every start s, length d and prototype p of an uncut recording (DESIGN.md
+// s3.10):
+//
+//   span_prefix   one thread per prototype: O[p, d], the duration term, in fp64
+//   span_fill     the entries with d > e (row 0 among them): -inf / -1
+//   span_nll      one workgroup per 32 consecutive starts: the running emission
+//                 sums E[s, p, d] of 32 starts x 32 prototypes in fp64, the best
+//                 prototype per (s, d) folded into the end-major output
+//   span_viterbi  one workgroup: the semi-Markov dynamic programme over the
+//                 output of span_nll and the backtrack
+//
+// span_nll is pair_nll's sliding-window sibling: the same staging, the same
+// per-term expressions and the same order of sums (a frame's F columns in
+// column order in fp32, frames in step order in fp64), with the frame of start
+// s at step t being row s + t of the recording.  No atomics, no device-global
+// word, and no workgroup waits for another.
+#include <climits>
+
+#include "abcd_common.h"
+#include "abcd_internal.h"
+#include "abcd_special.h"
+
+namespace abcd {
+
+constexpr int SP_TS = 32;      // starts per tile
+constexpr int SP_TP = 32;      // prototypes per tile
+constexpr int SP_FC = 64;      // columns staged per pass
+constexpr int SP_LD = SP_FC + 4;  // LDS row stride (16-byte aligned rows, staggered banks)
+constexpr int SP_MAX_D = 16383;
+
+DEV double softplus_d(double v) { return fmax(v, 0.0) + log1p(exp(-fabs(v))); }
+
+// O[p, d] = sum_{t < d - 1} sp(o[t, p]) + sp(-o[d - 1, p]) at Otab[(d - 1) P + p]: the prefix in step order,
+// then the last step's term
+__global__ __launch_bounds__(256) void span_prefix(const float* __restrict__ OL, int P, int D,
+                                                   double* __restrict__ Otab) {
+  const int p = blockIdx.x * 256 + threadIdx.x;
+  if (p >= P) return;
+  double cum = 0.0;
+  for (int t = 0; t < D; ++t) {
+    const double o = (double)OL[(long)t * P + p];
+    Otab[(long)t * P + p] = cum + softplus_d(-o);
+    cum += softplus_d(o);
+  }
+}
+
+// rows e <= min(N, D - 1): the entries with d > e
+__global__ __launch_bounds__(256) void span_fill(long rows, int D, double* __restrict__ span_score,
+                                                 int32_t* __restrict__ span_cat, long lds) {
+  const long at = (long)blockIdx.x * 256 + threadIdx.x;
+  if (at >= rows * D) return;
+  const long e = at / D;
+  const int c = (int)(at - e * D);  // d - 1
+  if (c < e) return;
+  span_score[e * lds + c] = -INFINITY;
+  span_cat[e * lds + c] = -1;
+}
+
+// What one thread holds of the next staging pass while the current one is
+// computed: its 8 rows x 1 column of x, mu and log_var.
+struct SpanRegs {
+  float x[SP_TS / 4], m[SP_TP / 4], l[SP_TP / 4];
+};
+
+// Workgroup blockIdx.x owns starts s0 = 32 blockIdx.x .. s0 + 31 and every
+// output entry (e = s + d, d) of theirs, so it max-combines the prototype tiles
+// itself, in tile order.  Per step t the 32 frame rows s0 + t .. s0 + t + 31
+// and the 32 prototype rows t P + p0 .. are staged, 64 columns at a time, as
+// pair_nll stages them (wave w takes rows w, w + 4, ... with its lanes on the
+// columns; e^-lv and 0.5 sum_f (log 2pi + lv) are formed once per staged
+// prototype element; the loads of pass i + 1 are in flight while pass i is
+// computed, two LDS images alternate, one barrier per pass).  Thread (i, j) =
+// (tid / 16, tid % 16) owns starts s0 + 2 i, + 1 and prototypes p0 + j, + 16.
+// After a step's last column chunk the 16 lanes that hold one start's 32
+// prototypes reduce (score, index) by shuffles, the lowest index winning a tie,
+// and lane j = 0 folds the result into the output entry: a plain store for the
+// first prototype tile, a read and a strict comparison for the later ones (the
+// same thread wrote what it reads).  Rows >= N, steps >= D, prototypes >= P
+// and columns >= F are not read.
+__global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, long ldx, long N, int F, int P, int D,
+                                                const float* __restrict__ MU, long ldm,
+                                                const float* __restrict__ LV, long ldl,
+                                                const double* __restrict__ Otab, const float* __restrict__ LW,
+                                                double* __restrict__ span_score, int32_t* __restrict__ span_cat,
+                                                long lds) {
+  __shared__ __attribute__((aligned(16))) float xs[2][SP_TS * SP_LD];
+  __shared__ __attribute__((aligned(16))) float ms[2][SP_TP * SP_LD];
+  __shared__ __attribute__((aligned(16))) float wsh[2][SP_TP * SP_LD];
+  __shared__ float cs[2][SP_TP];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const long s0 = (long)blockIdx.x * SP_TS;
+  const int nst = (int)min((long)D, N - s0);  // the tile's first start has the most steps
+  const int ti = tid >> 4, tj = tid & 15;
+  const int nch = (F + SP_FC - 1) / SP_FC;  // passes per step
+  const int nit = nst * nch;
+  for (int p0 = 0; p0 < P; p0 += SP_TP) {
+    SpanRegs g;
+    auto fetch = [&](int it) {
+      const int t = it / nch, c = it % nch, f = c * SP_FC + lane;
+      const bool fin = f < F;
+#pragma unroll
+      for (int i = 0; i < SP_TS / 4; ++i) {
+        const long row = s0 + t + w + 4 * i;
+        g.x[i] = (fin && row < N) ? X[row * ldx + f] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < SP_TP / 4; ++i) {
+        const int r = w + 4 * i;
+        const bool ok = fin && p0 + r < P;
+        const long row = (long)t * P + p0 + r;
+        g.m[i] = ok ? MU[row * ldm + f] : 0.f;
+        g.l[i] = ok ? LV[row * ldl + f] : 0.f;
+      }
+    };
+    const int pa = p0 + tj, pb = p0 + tj + 16;
+    const double lwa = (pa < P && LW) ? (double)LW[pa] : 0.0, lwb = (pb < P && LW) ? (double)LW[pb] : 0.0;
+    double em[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+    float q[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
+    float csum[SP_TP / 4];
+#pragma unroll
+    for (int i = 0; i < SP_TP / 4; ++i) csum[i] = 0.f;
+    fetch(0);
+    for (int it = 0; it < nit; ++it) {
+      const int t = it / nch, c = it % nch, f0 = c * SP_FC, k = it & 1;
+      const bool first = c == 0, last = c == nch - 1;
+      // ---- the fetched pass into LDS image k
+      {
+        const bool fin = f0 + lane < F;
+#pragma unroll
+        for (int i = 0; i < SP_TS / 4; ++i) xs[k][(w + 4 * i) * SP_LD + lane] = g.x[i];
+#pragma unroll
+        for (int i = 0; i < SP_TP / 4; ++i) {
+          const int r = w + 4 * i;
+          const bool ok = fin && p0 + r < P;
+          const float l = g.l[i];
+          ms[k][r * SP_LD + lane] = g.m[i];
+          wsh[k][r * SP_LD + lane] = ok ? __expf(-l) : 0.f;
+          const float cv = ok ? 1.8378770664093453f + l : 0.f;
+          csum[i] = first ? cv : csum[i] + cv;  // per lane: columns lane, lane + 64, ... in order
+        }
+        if (last) {  // the lanes' sums in a fixed tree
+#pragma unroll
+          for (int i = 0; i < SP_TP / 4; ++i) {
+            const float v = wave_sum(csum[i]);
+            if (lane == 0) cs[k][w + 4 * i] = 0.5f * v;
+          }
+        }
+      }
+      __syncthreads();
+      if (it + 1 < nit) fetch(it + 1);  // in flight while this pass is computed
+      // ---- compute from image k
+      if (first) q[0][0] = q[0][1] = q[1][0] = q[1][1] = 0.f;
+      const int n4 = (min(F - f0, SP_FC) + 3) >> 2;
+      const float4* x0 = (const float4*)(xs[k] + (2 * ti) * SP_LD);
+      const float4* x1 = (const float4*)(xs[k] + (2 * ti + 1) * SP_LD);
+      const float4* m0 = (const float4*)(ms[k] + tj * SP_LD);
+      const float4* m1 = (const float4*)(ms[k] + (tj + 16) * SP_LD);
+      const float4* w0 = (const float4*)(wsh[k] + tj * SP_LD);
+      const float4* w1 = (const float4*)(wsh[k] + (tj + 16) * SP_LD);
+#pragma unroll 2
+      for (int n = 0; n < n4; ++n) {
+        const float4 a0 = x0[n], a1 = x1[n], u0 = m0[n], u1 = m1[n], e0 = w0[n], e1 = w1[n];
+#define SP_TERM(Q, A, U, E)                                                          \
+  {                                                                                  \
+    float d = A.x - U.x; Q = fmaf(d * d, E.x, Q);                                    \
+    d = A.y - U.y; Q = fmaf(d * d, E.y, Q);                                          \
+    d = A.z - U.z; Q = fmaf(d * d, E.z, Q);                                          \
+    d = A.w - U.w; Q = fmaf(d * d, E.w, Q);                                          \
+  }
+        SP_TERM(q[0][0], a0, u0, e0)
+        SP_TERM(q[0][1], a0, u1, e1)
+        SP_TERM(q[1][0], a1, u0, e0)
+        SP_TERM(q[1][1], a1, u1, e1)
+#undef SP_TERM
+      }
+      if (last) {  // the frame is complete: one fp32 value per (start, prototype) joins the fp64 sum
+        const float c0 = cs[k][tj], c1 = cs[k][tj + 16];
+        const double oa = pa < P ? Otab[(long)t * P + pa] : 0.0, ob = pb < P ? Otab[(long)t * P + pb] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const long e = s0 + 2 * ti + i + t + 1;  // the end of start s0 + 2 ti + i at length t + 1
+          const bool v = e <= N;
+          if (v) {
+            em[i][0] += (double)(c0 + 0.5f * q[i][0]);
+            em[i][1] += (double)(c1 + 0.5f * q[i][1]);
+          }
+          double sa = pa < P ? lwa - em[i][0] - oa : -INFINITY;
+          double sb = pb < P ? lwb - em[i][1] - ob : -INFINITY;
+          int arg = pa, ab = pb;
+          if (!(sa > -INFINITY)) { sa = -INFINITY; arg = INT_MAX; }  // NaN and -inf: excluded
+          if (!(sb > -INFINITY)) { sb = -INFINITY; ab = INT_MAX; }
+          if (sb > sa) { sa = sb; arg = ab; }
+#pragma unroll
+          for (int o = 8; o > 0; o >>= 1) {  // the 16 lanes of one start
+            const double s2 = __shfl_xor(sa, o, 64);
+            const int a2 = __shfl_xor(arg, o, 64);
+            const bool take = (s2 > sa) | ((s2 == sa) & (a2 < arg));  // no short-circuit: selects, not branches
+            sa = take ? s2 : sa;
+            arg = take ? a2 : arg;
+          }
+          if (tj == 0 && v) {
+            const long at = e * lds + t;
+            if (p0 == 0) {
+              span_score[at] = sa;
+              span_cat[at] = arg == INT_MAX ? -1 : arg;
+            } else if (sa > span_score[at]) {  // a later tile holds higher indices: it needs a strictly better score
+              span_score[at] = sa;
+              span_cat[at] = arg;
+            }
+          }
+        }
+      }
+    }
+    __syncthreads();  // the next prototype tile starts over at image 0
+  }
+}
+
+constexpr int SV_THREADS = 256;  // the widest launch; D <= SV_ONE_WAVE_D runs as a single wave
+constexpr int SV_ONE_WAVE_D = 256;
+constexpr int SV_PRE = 4;  // span entries per thread loaded one step ahead (D <= 4 x the launch width runs from registers)
+
+// One workgroup, one launch: V[n] for n = 1 .. N, then the backtrack.
+//   V[n] = max(V[n-1] + gap[n-1], max_{d_min <= d <= min(D, n)} (V[n-d] + span[n, d]) + bonus)
+// Lanes stride over d; each thread's candidates in ascending d under a strict
+// comparison, then a wave shuffle tree and the waves in order, the smaller d
+// winning a tie; the gap wins a tie against the segment.  The step is a chain
+// of dependent latencies, not throughput: up to D = 256 one wave takes four
+// candidates per lane and its barrier and LDS exchange cost next to nothing;
+// wider D runs on four waves.  NaN
+// candidates fail every comparison.  V lives in a ring of D doubles in LDS.
+// Every thread forms V[n] itself from the wave results, so the candidate
+// d = 1 comes from a register and the ring entry thread 0 stores after barrier
+// n is first read after barrier n + 1: one barrier per step.  The span row and
+// the gap of step n + 1 do not depend on V and are loaded while step n reduces.
+__global__ __launch_bounds__(SV_THREADS) void span_viterbi(const double* __restrict__ SS,
+                                                           const int32_t* __restrict__ SC, long lds, long N, int D,
+                                                           int dmin, const float* __restrict__ gap, double bonus,
+                                                           double* __restrict__ path_score,
+                                                           int32_t* __restrict__ n_segments,
+                                                           int32_t* __restrict__ seg_onset,
+                                                           int32_t* __restrict__ seg_length,
+                                                           int32_t* __restrict__ seg_cat, double* __restrict__ seg_score,
+                                                           double* __restrict__ V_out, int32_t* __restrict__ back) {
+  extern __shared__ __attribute__((aligned(16))) double ring[];  // V[n] at n mod D
+  __shared__ double wb[2][SV_THREADS / 64];
+  __shared__ int wd[2][SV_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nt = blockDim.x, nw = nt >> 6;
+  if (tid == 0) {
+    ring[0] = 0.0;
+    back[0] = 0;
+    if (V_out) V_out[0] = 0.0;
+  }
+  __syncthreads();
+  double vprev = 0.0;
+  double pre[SV_PRE];
+  float gnext = 0.f;
+  auto load_row = [&](long n) {
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) {
+      const int d = tid + 1 + nt * r;  // an unconditional load from a clamped index: no branch, a counted wait
+      pre[r] = SS[n * lds + min(d, D) - 1];  // used one step later, under the candidate's own mask
+    }
+    if (gap) gnext = gap[n - 1];
+  };
+  if (N >= 1) load_row(1);
+  int pos = 0;  // (n - 1) mod D
+  for (long n = 1; n <= N; ++n) {
+    double cur[SV_PRE];
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) cur[r] = pre[r];
+    const double gapc = gap ? vprev + (double)gnext : -INFINITY;
+    if (n < N) load_row(n + 1);
+    pos = pos + 1 == D ? 0 : pos + 1;  // n mod D
+    const int dmax = (int)min((long)D, n);
+    double best = -INFINITY;
+    int bd = INT_MAX;
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) {
+      const int d = tid + 1 + nt * r;
+      int at = pos - min(d, D);
+      at += at < 0 ? D : 0;
+      const double v = ring[at];  // a slot not written yet (d > n) is read and masked
+      const double c = (d == 1 ? vprev : v) + cur[r];
+      const bool take = (d >= dmin) & (d <= dmax) & (c > best);
+      best = take ? c : best;
+      bd = take ? d : bd;
+    }
+    for (int d = tid + 1 + nt * SV_PRE; d <= dmax; d += nt) {
+      if (d < dmin) continue;
+      int at = pos - d;
+      if (at < 0) at += D;
+      const double c = ring[at] + SS[n * lds + d - 1];
+      if (c > best) { best = c; bd = d; }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double b2 = __shfl_xor(best, o, 64);
+      const int d2 = __shfl_xor(bd, o, 64);
+      const bool take = (b2 > best) | ((b2 == best) & (d2 < bd));  // no short-circuit: selects, not branches
+      best = take ? b2 : best;
+      bd = take ? d2 : bd;
+    }
+    const int k = (int)(n & 1);
+    if (lane == 0) { wb[k][w] = best; wd[k][w] = bd; }
+    __syncthreads();
+    best = wb[k][0];
+    bd = wd[k][0];
+    for (int i = 1; i < nw; ++i) {
+      const double b2 = wb[k][i];
+      const int d2 = wd[k][i];
+      if (b2 > best || (b2 == best && d2 < bd)) { best = b2; bd = d2; }
+    }
+    const double seg = best + bonus;
+    const bool vg = gapc > -INFINITY, vs = seg > -INFINITY && bd != INT_MAX;
+    double V = -INFINITY;
+    int choice = 0;  // 0: the gap (or nothing); d: a segment of d frames ends here
+    if (vg && (!vs || gapc >= seg)) V = gapc;
+    else if (vs) { V = seg; choice = bd; }
+    vprev = V;
+    if (tid == 0) {
+      ring[pos] = V;
+      back[n] = choice;
+      if (V_out) V_out[n] = V;
+    }
+  }
+  if (tid != 0) return;
+  if (!(vprev > -INFINITY)) {  // the end cannot be reached
+    *path_score = -INFINITY;
+    *n_segments = 0;
+    return;
+  }
+  int count = 0;
+  for (long n = N; n > 0;) {
+    const int d = back[n];
+    if (d == 0) { --n; } else { ++count; n -= d; }
+  }
+  int i = count;
+  for (long n = N; n > 0;) {
+    const int d = back[n];
+    if (d == 0) { --n; continue; }
+    --i;
+    seg_onset[i] = (int32_t)(n - d);
+    seg_length[i] = d;
+    seg_cat[i] = SC[n * lds + d - 1];
+    seg_score[i] = SS[n * lds + d - 1];
+    n -= d;
+  }
+  *n_segments = count;
+  *path_score = vprev;
+}
+
+static bool span_shape_ok(long N, int D) {
+  return D >= 1 && D <= SP_MAX_D && N >= 0 && N < (1L << 31) && (N + 1) * (long)D < (1L << 31);
+}
+
+}  // namespace abcd
+
+using namespace abcd;
+
+extern "C" size_t abcd_span_scores_workspace_bytes(long N, int D, int P) {
+  if (!span_shape_ok(N, D) || P < 1) return 0;
+  return (size_t)D * (size_t)P * sizeof(double) + 256;  // O[p, d]
+}
+
+extern "C" int abcd_span_scores(const float* x, long ld_x, long N, int F, int P, int D, int T_proto,
+                                const float* proto_mu, long ld_mu, const float* proto_lv, long ld_lv,
+                                const float* proto_offset_logits, const float* log_weight, double* span_score,
+                                int32_t* span_cat, long ld_span, void* ws, size_t ws_bytes, void* stream) {
+  ABCD_REQUIRE(span_shape_ok(N, D) && P >= 1 && F >= 1 && T_proto >= D);
+  ABCD_REQUIRE(ld_x >= F && ld_mu >= F && ld_lv >= F && ld_span >= D);
+  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits && span_score && span_cat));
+  const size_t need = abcd_span_scores_workspace_bytes(N, D, P);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  if (!span_score || !span_cat) return 0;  // N = 0 with nowhere to write row 0
+  hipStream_t s = (hipStream_t)stream;
+  const long rows = std::min(N, (long)D - 1) + 1;
+  span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, ld_span);
+  ABCD_CHECK_LAUNCH();
+  if (N == 0) return 0;
+  double* Otab = (double*)ws;
+  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
+  span_nll<<<cdiv(N, SP_TS), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab, log_weight,
+                                          span_score, span_cat, ld_span);
+  ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t abcd_span_viterbi_workspace_bytes(long N, int D) {
+  if (!span_shape_ok(N, D)) return 0;
+  return ((size_t)N + 1) * sizeof(int32_t) + 256;  // the back-pointers
+}
+
+extern "C" int abcd_span_viterbi(const double* span_score, const int32_t* span_cat, long ld_span, long N, int D,
+                                 int d_min, const float* gap, double seg_bonus, double* path_score,
+                                 int32_t* n_segments, int32_t* seg_onset, int32_t* seg_length, int32_t* seg_cat,
+                                 double* seg_score, double* V_out, void* ws, size_t ws_bytes, void* stream) {
+  ABCD_REQUIRE(span_shape_ok(N, D) && d_min >= 1 && d_min <= D && ld_span >= D);
+  ABCD_REQUIRE(N == 0 || (span_score && span_cat && path_score && n_segments && seg_onset && seg_length && seg_cat &&
+                          seg_score));
+  const size_t need = abcd_span_viterbi_workspace_bytes(N, D);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) {  // the empty path: score 0, no segments, nothing is read
+    if (path_score) ABCD_TRY(hipMemsetAsync(path_score, 0, sizeof(double), s));
+    if (n_segments) ABCD_TRY(hipMemsetAsync(n_segments, 0, sizeof(int32_t), s));
+    if (V_out) ABCD_TRY(hipMemsetAsync(V_out, 0, sizeof(double), s));
+    return 0;
+  }
+  static bool attr = false;
+  if (!attr) {
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_viterbi, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (SP_MAX_D + 1) * (int)sizeof(double)));
+    attr = true;
+  }
+  span_viterbi<<<1, D <= SV_ONE_WAVE_D ? 64 : SV_THREADS, (size_t)D * sizeof(double), s>>>(span_score, span_cat, ld_span, N, D, d_min, gap,
+                                                                 seg_bonus, path_score, n_segments, seg_onset,
+                                                                 seg_length, seg_cat, seg_score, V_out, (int32_t*)ws);
+  ABCD_CHECK_LAUNCH();
+  return 0;
+}

@@ -159,6 +159,13 @@ _SIGS = {
     "abcd_chain_posterior": (c_int, [c_void_p, c_long, c_long, c_int, c_void_p, c_int, c_void_p, c_long, c_void_p,
                                      c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
+    "abcd_span_scores_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "abcd_span_scores": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_int, c_void_p, c_long, c_void_p,
+                                 c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_size_t, c_void_p]),
+    "abcd_span_viterbi_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "abcd_span_viterbi": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_int, c_void_p, c_double, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
     "abcd_stft_frames": (c_int, [ctypes.c_longlong, c_int, c_int, c_int]),
     "abcd_featurize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "abcd_featurize_packed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float,
@@ -245,7 +252,8 @@ def source_hash():
     import hashlib
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     names = ["abcd_gemm.hip", "abcd_rnn.hip", "abcd_persist.hip", "abcd_sampler.hip", "abcd_optim.hip",
-             "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_vocoder.hip", "abcd_chain.hip", "abcd_common.h",
+             "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_vocoder.hip", "abcd_chain.hip", "abcd_span.hip",
+             "abcd_common.h",
              "abcd_internal.h",
              "abcd_persist.h", "abcd_special.h", "abcd_x6.h", "../../include/abcd_hip.h"]
     h = hashlib.sha256()

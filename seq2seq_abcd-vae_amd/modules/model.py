@@ -872,6 +872,33 @@ class RNN_Variational_Decoder(torch.nn.Module):
             lengths = (bs[None, :] > torch.arange(int(bs[0]))[:, None]).sum(1).to(dev)
         return em, (off if gt_off is not None else None), lengths
 
+    def span_scores(self, prototypes, frames, max_length, log_weight=None):
+        """Every span of an uncut recording against every prototype:
+        ``(span_score, span_cat)``, both ``N + 1 x max_length`` and end-major,
+        with ``span_score[e, d - 1]`` (float64) the largest ``log_weight[p] -
+        em - off`` over the prototypes p of ``prototypes`` (what
+        ``prototypes()`` returned, decoded for at least ``max_length`` steps)
+        for frames ``e - d .. e - 1`` of ``frames`` (N x F) taken as one
+        segment that ends after d frames -- what ``score_against`` gives for
+        that cut with a one-hot end target -- and ``span_cat`` (int32) the
+        lowest p attaining it.  Entries with ``d > e`` hold -inf / -1.
+        Forward-only, under ``torch.no_grad()``."""
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(frames)
+        F, D = self.rnn_cell.cell.input_size, int(max_length)
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= D >= 1):
+            raise ValueError(f"span_scores: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
+        if frames.dim() != 2 or frames.shape[1] != F:
+            raise ValueError(f"span_scores: frames must be N x {F}, got {tuple(frames.shape)}")
+        P = int(offl.shape[1])
+        with torch.no_grad():
+            score, cat = ops.span_scores(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F), offl.reshape(-1),
+                                         log_weight, P, D)
+        return score, cat
+
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()
         return torch.tensor([int((lengths > t).sum()) for t in range(int(lengths.max()))], dtype=torch.int64)

@@ -27,9 +27,11 @@ operator                   replaces (reference)                            C ent
 ``abcd::pair_posterior``   (none: responsibilities, evidence, argmax)      ``abcd_pair_posterior``
 ``abcd::griffin_lim``      (none: log-spectra back to audio)               ``abcd_griffin_lim``
 ``abcd::chain_posterior``  (none: an HMM over category sequences)          ``abcd_chain_posterior``
+``abcd::span_scores``      (none: every span of an uncut recording)        ``abcd_span_scores``
+``abcd::span_viterbi``     (none: the best cover by segments)              ``abcd_span_viterbi``
 =========================  ==============================================  =========================================
 
-The last six are forward-only (scoring, synthesis): they have no autograd
+The last eight are forward-only (scoring, synthesis, segmentation): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -858,6 +860,123 @@ _forward_only(chain_posterior, "chain_posterior")
 
 
 # ----------------------------------------------------------------------------
+# segmentation: span scores of an uncut recording and the semi-Markov programme (forward-only)
+# ----------------------------------------------------------------------------
+@torch.library.custom_op("abcd::span_scores", mutates_args=())
+def span_scores(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_logits: Tensor,
+                log_weight: Optional[Tensor], P: int, D: int) -> List[Tensor]:
+    """-> [span_score (N + 1 x D, fp64), span_cat (N + 1 x D, int32)], end-major:
+    entry [e, d - 1] is the best prototype's log-likelihood of frames e - d ..
+    e - 1 (N x F, row-strided views pass without a copy) being one segment that
+    ends after d frames, and that prototype (abcd_span_scores).  The prototypes
+    are the time-major rectangle pairwise_nll takes, T_proto >= D; entries with
+    d > e, and spans with every prototype excluded, hold -inf / -1."""
+    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
+        N.require_gpu(t)
+    P, D = int(P), int(D)
+    if frames.dim() != 2 or frames.shape[1] < 1:
+        raise ValueError(f"span_scores: frames must be N x F, got {tuple(frames.shape)}")
+    n, F = (int(v) for v in frames.shape)
+    if P < 1 or D < 1:
+        raise ValueError("span_scores: P and D must be at least 1")
+    dev = frames.device
+    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
+    ol = proto_offset_logits.float().contiguous()
+    rows = int(ol.numel())
+    if rows % P or rows // P < D:
+        raise ValueError(f"span_scores: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
+                         f"got {rows}")
+    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
+        raise ValueError(f"span_scores: proto_mu and proto_lv must be {(rows, F)}")
+    lw = None
+    if log_weight is not None:
+        N.require_gpu(log_weight)
+        if log_weight.numel() != P:
+            raise ValueError(f"span_scores: log_weight must hold {P} entries, got {log_weight.numel()}")
+        lw = log_weight.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_span_scores_workspace_bytes(n, D, P)
+    if nbytes == 0:
+        raise N.HipError("span_scores: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
+    ws = N.workspace(nbytes, dev)
+    score = torch.empty(n + 1, D, dtype=torch.float64, device=dev)
+    cat = torch.empty(n + 1, D, dtype=torch.int32, device=dev)
+    N.check(L_.abcd_span_scores(N.ptr(x), ldx, n, F, P, D, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                                N.ptr(lw), N.ptr(score), N.ptr(cat), D, N.ptr(ws), ws.numel(), N.stream()),
+            "span scores")
+    return [score, cat]
+
+
+@span_scores.register_fake
+def _(frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D):
+    n = frames.shape[0]
+    return [frames.new_empty(n + 1, int(D), dtype=torch.float64), frames.new_empty(n + 1, int(D), dtype=torch.int32)]
+
+
+_forward_only(span_scores, "span_scores")
+
+
+@torch.library.custom_op("abcd::span_viterbi", mutates_args=())
+def span_viterbi(span_score: Tensor, span_cat: Tensor, d_min: int, gap: Optional[Tensor], seg_bonus: float,
+                 want_v: bool) -> List[Tensor]:
+    """-> [path_score (0-d, fp64), n_segments (0-d, int32), onset, length,
+    category (N // d_min each, int32), score (N // d_min, fp64), V (N + 1 fp64,
+    or empty)]: the best cover of the N frames by non-overlapping segments of
+    d_min .. D frames and gap frames under span_scores' table (N + 1 x D,
+    row-strided views pass without a copy), abcd_span_viterbi.  Only the first
+    n_segments entries of the segment lists are written."""
+    N.require_gpu(span_score)
+    N.require_gpu(span_cat)
+    if span_score.dim() != 2 or span_score.shape[0] < 1 or span_score.shape[1] < 1 or \
+            tuple(span_cat.shape) != tuple(span_score.shape):
+        raise ValueError(f"span_viterbi: span_score and span_cat must both be N + 1 x D, got "
+                         f"{tuple(span_score.shape)} and {tuple(span_cat.shape)}")
+    n, D = int(span_score.shape[0]) - 1, int(span_score.shape[1])
+    d_min = int(d_min)
+    if d_min < 1 or d_min > D:
+        raise ValueError(f"span_viterbi: d_min must lie in 1 .. {D}, got {d_min}")
+    dev = span_score.device
+    ss, ld = _rows(span_score.double())
+    sc, ldc = _rows(span_cat.to(torch.int32))
+    if ldc != ld:  # one row stride serves both
+        ss, sc, ld = ss.contiguous(), sc.contiguous(), D
+    g = None
+    if gap is not None:
+        N.require_gpu(gap)
+        if gap.numel() != n:
+            raise ValueError(f"span_viterbi: gap must hold {n} entries, got {gap.numel()}")
+        g = gap.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_span_viterbi_workspace_bytes(n, D)
+    if nbytes == 0:
+        raise N.HipError("span_viterbi: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
+    ws = N.workspace(nbytes, dev)
+    cap = n // d_min
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    ps, ns = torch.empty((), **f64), torch.empty((), **i32)
+    onset, length, cat = (torch.zeros(max(cap, 1), **i32) for _ in range(3))
+    score = torch.zeros(max(cap, 1), **f64)
+    V = torch.empty(n + 1 if want_v else 0, **f64)
+    N.check(L_.abcd_span_viterbi(N.ptr(ss), N.ptr(sc), ld, n, D, d_min, N.ptr(g), float(seg_bonus), N.ptr(ps),
+                                 N.ptr(ns), N.ptr(onset), N.ptr(length), N.ptr(cat), N.ptr(score),
+                                 N.ptr(V) if want_v else None, N.ptr(ws), ws.numel(), N.stream()), "span viterbi")
+    return [ps, ns, onset[:cap], length[:cap], cat[:cap], score[:cap], V]
+
+
+@span_viterbi.register_fake
+def _(span_score, span_cat, d_min, gap, seg_bonus, want_v):
+    n = span_score.shape[0] - 1
+    cap = n // int(d_min)
+    e = span_score.new_empty
+    return [e((), dtype=torch.float64), e((), dtype=torch.int32), e(cap, dtype=torch.int32),
+            e(cap, dtype=torch.int32), e(cap, dtype=torch.int32), e(cap, dtype=torch.float64),
+            e(n + 1 if want_v else 0, dtype=torch.float64)]
+
+
+_forward_only(span_viterbi, "span_viterbi")
+
+
+# ----------------------------------------------------------------------------
 # log-spectra back to audio (forward-only)
 # ----------------------------------------------------------------------------
 @torch.library.custom_op("abcd::griffin_lim", mutates_args=())
@@ -911,7 +1030,7 @@ _forward_only(griffin_lim, "griffin_lim")
 
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
-       "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior")
+       "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi")
 
 
 def registered() -> Sequence[str]:

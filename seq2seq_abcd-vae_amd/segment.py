@@ -1,0 +1,267 @@
+# coding: utf-8
+"""Segmentation on the HIP path: cut uncut recordings into labelled segments
+with a trained ABCD-VAE's decoder.
+
+Every other entry point starts from an annotation table that already gives each
+segment's onset and offset.  This script needs the recordings only.  The K
+categories are decoded once as prototypes (``classify.Classifier.prototypes_for``);
+the end-of-segment logits make them a duration model, so ``log p(frames s .. s
++ d - 1, ends after d | category k)`` is defined for every start, length and
+category of a recording (``RNN_Variational_Decoder.span_scores``), and a
+semi-Markov dynamic programme picks the best cover of the recording by
+non-overlapping segments (``modules.segmentation.segment_frames``).  Frames no
+segment covers cost ``--gap_score`` each, or their log-likelihood under a
+diagonal Gaussian background (``--gap_model``, fitted from the uncovered frames
+of an existing annotation by ``--fit_gap``); without either the segments tile
+the recording.
+
+Same checkpoint, STFT, epsilon, normaliser and channel arguments as
+``classify.py``.  The input table needs an ``input_path`` column only (an
+existing annotation works: its distinct paths are used); each recording is
+featurised whole.  Output: an annotation CSV in the reference's format,
+
+``onset, offset, input_path, data_type, speaker, label, category_ix, length,
+segment_score``
+
+with times in seconds and ``label`` = ``category_ix``, which feeds straight into
+``encode.py``, ``classify.py``, ``sequence.py`` or ``learning.py``.  A segment of
+frames ``s .. s + d - 1`` is written as samples ``s hop .. (s + d - 1) hop +
+(hop - 1) // 2`` (plus the window length without centring), which the package's
+loader turns into exactly d frames again.  The loader pads each segment at its
+own edges, so the frames nearest a boundary differ from the whole-recording
+frames this script scored: ``classify.py`` on the result can disagree with
+``category_ix`` there."""
+import os
+import sys
+
+import numpy as np
+import pandas as pd
+import scipy.io.wavfile as spw
+import torch
+
+import classify
+from encode import rename_existing_file
+from modules import _native, data_utils, segmentation
+
+COLUMNS = ("onset", "offset", "input_path", "data_type", "speaker", "label", "category_ix", "length", "segment_score")
+
+
+def num_frames(samples, frame, hop, centering=True):
+    """Frames ``torch.stft`` gives for ``samples`` samples."""
+    return 1 + samples // hop if centering else (1 + (samples - frame) // hop if samples >= frame else 0)
+
+
+def min_loadable_length(frame, hop, centering=True):
+    """The shortest segment (frames) the loader can featurise again: the
+    centred STFT reflects frame // 2 samples at each edge and needs more
+    samples than that."""
+    if not centering:
+        return 1
+    d = 1
+    while frames_to_samples(0, d, frame, hop, True)[1] <= frame // 2:
+        d += 1
+    return d
+
+
+def frames_to_samples(onset, length, frame, hop, centering=True, total=None):
+    """(onset_ix, offset_ix) in samples of the segment of frames ``onset ..
+    onset + length - 1`` of a whole-recording STFT, such that the loader's cut
+    ``wav[onset_ix:offset_ix]`` has exactly ``length`` frames, centred on (or
+    starting at) the same samples.  The cut ends in the middle of the range of
+    sample counts that give ``length`` frames, so rounding a time by one sample
+    does not change the count; ``total`` (the recording's samples) clips it."""
+    on = int(onset) * hop
+    off = (int(onset) + int(length) - 1) * hop + (hop - 1) // 2 + (0 if centering else frame)
+    if total is not None:
+        off = min(off, int(total))
+    return on, off
+
+
+def covered_frames(n_frames, onsets, offsets, fs, frame, hop, centering=True):
+    """N booleans: whether a frame of the whole-recording STFT lies inside one
+    of the annotated segments (seconds), by its centre sample (centred STFT) or
+    by any overlap of its window."""
+    at = np.arange(n_frames, dtype=np.int64) * hop
+    mask = np.zeros(n_frames, dtype=bool)
+    for on, off in zip(np.round(np.asarray(onsets) * fs), np.round(np.asarray(offsets) * fs)):
+        mask |= ((at >= on) & (at <= off)) if centering else ((at < off) & (at + frame > on))
+    return mask
+
+
+def segment_rows(input_path, onset, length, category, score, fs, frame, hop, centering, total, data_type="segmented",
+                 speaker=float("nan")):
+    """The table rows of one recording's segments (frame units -> seconds)."""
+    rows = []
+    for s, d, k, v in zip(onset, length, category, score):
+        on, off = frames_to_samples(s, d, frame, hop, centering, total)
+        rows.append({"onset": on / fs, "offset": off / fs, "input_path": input_path, "data_type": data_type,
+                     "speaker": speaker, "label": int(k), "category_ix": int(k), "length": int(d),
+                     "segment_score": float(v)})
+    return rows
+
+
+def write_segments(save_path, rows):
+    """Writes the annotation table (an existing file is kept as .prev, nothing
+    partial is left behind).  Returns the number of rows."""
+    df = pd.DataFrame(rows, columns=list(COLUMNS))
+    tmp = save_path + ".partial"
+    try:
+        df.to_csv(tmp, index=False)
+    except BaseException:
+        if os.path.isfile(tmp):
+            os.remove(tmp)
+        raise
+    rename_existing_file(save_path)
+    os.replace(tmp, save_path)
+    return len(df)
+
+
+def read_wave(input_root, input_path, channel=0):
+    fs, data = spw.read(os.path.join(input_root, input_path))
+    if data.ndim > 1:
+        data = data[:, channel]
+    return fs, np.ascontiguousarray(data).astype(np.float32)
+
+
+class Segmenter(classify.Classifier):
+    """A trained ABCD checkpoint opened for segmentation."""
+
+    def segment_recording(self, frames, max_length, min_length=1, log_weight=None, gap=None, seg_bonus=0.0,
+                          speaker=None):
+        """``segmentation.segment_frames`` of one recording's frames under the
+        categories' prototypes (of ``speaker`` when the decoder embeds speakers)."""
+        if self.decoder.embed_speaker is not None and speaker is None:
+            raise ValueError("this decoder embeds speakers: a speaker index is required")
+        protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(max_length))
+        return segmentation.segment_frames(self.decoder, protos, frames.to(self.device), max_length,
+                                           min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus)
+
+
+def get_parameters(argv=None):
+    import argparse
+    p = argparse.ArgumentParser(description="Cut recordings into labelled segments with a trained ABCD-VAE's decoder "
+                                            "(MI355X): span scores under every category and a semi-Markov cover.")
+    p.add_argument("model_path", type=str, help="checkpoint.pt written by learning.py (this package or the reference)")
+    p.add_argument("input_root", type=str, help="directory the table's wav paths are relative to")
+    p.add_argument("recording_table", type=str,
+                   help="table (csv) with an input_path column; an existing annotation works (its distinct paths)")
+    p.add_argument("data_normalizer", type=float, help="log-amplitudes are divided by this (training's -N)")
+    p.add_argument("--annotation_sep", type=str, default=",", help="field separator of the tables")
+    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
+    p.add_argument("-S", "--save_path", type=str, default=None,
+                   help="output csv (default: <input_root>/segmented.csv); an existing file is kept as .prev")
+    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
+    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
+    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
+    p.add_argument("--fft_no_centering", action="store_true", help="STFT without centre padding")
+    p.add_argument("--channel", type=int, default=0, help="channel (0-based) of multi-channel wav files")
+    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
+    p.add_argument("--max_length", type=int, required=True, help="longest segment, frames")
+    p.add_argument("--min_length", type=int, default=1,
+                   help="shortest segment, frames (raised to the shortest the loader can featurise again)")
+    p.add_argument("--prior", type=str, default="dirichlet", choices=classify.PRIORS,
+                   help="log weights of the categories: the Dirichlet posterior's E[log pi_k] (default) or zero")
+    p.add_argument("--entire_data_size", type=float, default=None,
+                   help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the table's rows)")
+    p.add_argument("--segment_bonus", type=float, default=0.0,
+                   help="log prior added per segment; negative values discourage over-segmentation")
+    p.add_argument("--gap_score", type=float, default=None,
+                   help="constant log-likelihood of a frame no segment covers (default: none, the segments tile "
+                        "the recording)")
+    p.add_argument("--gap_model", type=str, default=None,
+                   help="npz with mu and log_var (F each): a diagonal Gaussian background for uncovered frames")
+    p.add_argument("--fit_gap", type=str, default=None,
+                   help="annotation table: fit the background from the frames its segments leave uncovered, write "
+                        "it to --gap_model_out and use it")
+    p.add_argument("--gap_model_out", type=str, default=None, help="where --fit_gap writes the npz")
+    p.add_argument("--speaker", type=int, default=None,
+                   help="speaker index; required when the decoder embeds speakers")
+    a = p.parse_args(argv)
+    if a.max_length < 1 or a.max_length > 16383:
+        p.error("--max_length must lie in 1 .. 16383")
+    if a.min_length < 1 or a.min_length > a.max_length:
+        p.error("--min_length must lie in 1 .. --max_length")
+    if a.entire_data_size is not None and not a.entire_data_size > 0:
+        p.error("--entire_data_size must be positive")
+    if sum(v is not None for v in (a.gap_score, a.gap_model, a.fit_gap)) > 1:
+        p.error("--gap_score, --gap_model and --fit_gap exclude one another")
+    if (a.fit_gap is None) != (a.gap_model_out is None):
+        p.error("--fit_gap and --gap_model_out go together")
+    return a
+
+
+def main(argv=None):
+    a = get_parameters(argv)
+    save_path = a.save_path or os.path.join(a.input_root, "segmented.csv")
+    for path in (save_path, a.gap_model_out):
+        if path and os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+    table = pd.read_csv(a.recording_table, sep=a.annotation_sep)
+    if "input_path" not in table.columns:
+        raise SystemExit(f"{a.recording_table}: no input_path column")
+    paths = list(dict.fromkeys(table["input_path"].tolist()))
+    seg = Segmenter(a.model_path, device=a.device)
+    if seg.decoder.embed_speaker is not None and a.speaker is None:
+        raise SystemExit("this checkpoint's decoder embeds speakers: --speaker is required")
+    centering = not a.fft_no_centering
+    eps, norm = a.epsilon, a.data_normalizer
+    stft = {}
+
+    def featurise(path):
+        fs, wave = read_wave(a.input_root, path, a.channel)
+        frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))
+        if (frame, hop) not in stft:
+            stft[frame, hop] = data_utils.STFT(frame, hop, window=a.fft_window_type, centering=centering)
+        frames = (stft[frame, hop](torch.from_numpy(wave)) + eps).log() / norm
+        return fs, frame, hop, len(wave), frames.to(seg.device)
+
+    gap_model = None
+    if a.fit_gap is not None:
+        ann = pd.read_csv(a.fit_gap, sep=a.annotation_sep)
+        kept = []
+        for path, sub in ann.groupby("input_path"):
+            fs, frame, hop, _, frames = featurise(path)
+            mask = covered_frames(frames.shape[0], sub.onset.to_numpy(), sub.offset.to_numpy(), fs, frame, hop,
+                                  centering)
+            kept.append(frames[torch.from_numpy(~mask).to(frames.device)])
+        kept = torch.cat(kept)
+        gap_model = segmentation.fit_gap_model(kept, torch.zeros(kept.shape[0], dtype=torch.bool))
+        np.savez(a.gap_model_out, mu=gap_model[0].cpu().numpy(), log_var=gap_model[1].cpu().numpy())
+    elif a.gap_model is not None:
+        with np.load(a.gap_model) as z:
+            gap_model = (torch.from_numpy(z["mu"]), torch.from_numpy(z["log_var"]))
+
+    lw = seg.log_weight(a.prior, len(table) if a.entire_data_size is None else a.entire_data_size)
+    rows = []
+    for path in paths:
+        fs, frame, hop, total, frames = featurise(path)
+        d_min = max(a.min_length, min_loadable_length(frame, hop, centering))
+        if d_min > a.min_length:
+            print(f"{path}: --min_length raised from {a.min_length} to {d_min} frames, the shortest segment the "
+                  "loader can featurise", file=sys.stderr)
+        if d_min > a.max_length:
+            raise SystemExit(f"{path}: --max_length {a.max_length} is below the shortest loadable segment ({d_min})")
+        gap = None
+        if a.gap_score is not None:
+            gap = torch.full((frames.shape[0],), float(a.gap_score), device=seg.device)
+        elif gap_model is not None:
+            gap = segmentation.gap_scores(frames, *gap_model)
+        out = seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
+                                    seg_bonus=a.segment_bonus, speaker=a.speaker)
+        if not bool(out["path_score"] > float("-inf")):
+            print(f"{path}: no cover of its {frames.shape[0]} frames by segments of {d_min} .. {a.max_length} "
+                  "frames (give a gap score or model)", file=sys.stderr)
+        first = table[table["input_path"] == path].iloc[0]
+        speaker = first["speaker"] if "speaker" in table.columns else (
+            float("nan") if a.speaker is None else a.speaker)
+        data_type = first["data_type"] if "data_type" in table.columns else "segmented"
+        rows += segment_rows(path, out["onset"].tolist(), out["length"].tolist(), out["category"].tolist(),
+                             out["score"].tolist(), fs, frame, hop, centering, total, data_type=data_type,
+                             speaker=speaker)
+    _native.op_status.sync("segment")
+    write_segments(save_path, rows)
+    return save_path
+
+
+if __name__ == "__main__":
+    main()
