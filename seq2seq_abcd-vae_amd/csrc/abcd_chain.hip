@@ -337,6 +337,8 @@ __global__ __launch_bounds__(CH_THREADS) void chain_kernel(ChainArgs a) {
           const int j = tid + CH_THREADS * n;
           if (j < K && va[j] > bv) { bv = va[j]; bi = j; }
         }
+        // wave_argmax (abcd_special.h) written out, with a branch: with the selects of the shared form the
+        // Viterbi-only call measured 1.2 % slower at K = 128 (1357 against 1339 us) in two sessions
         for (int o = 32; o > 0; o >>= 1) {
           const float v2 = __shfl_xor(bv, o, 64);
           const int i2 = __shfl_xor(bi, o, 64);

@@ -14,178 +14,96 @@
 //                   fp64, responsibilities, the best prototype
 //
 // The per-term expressions are those of dec_emission_nll / dec_offset_head
-// (abcd_rnn.hip) as seg_losses (abcd_score.hip) repeats them.  Every sum has a
-// fixed order: a frame's F columns in column order in fp32, the frames of a
-// slice in step order in fp64, the slices in slice order in fp64.  No atomics,
-// no device-global word, and no workgroup waits for another.
+// (abcd_rnn.hip) as seg_losses (abcd_score.hip) repeats them; pair_nll's
+// emission half (staging, pipelining, the 2 x 2 accumulation) is the tile of
+// abcd_emtile.h, which span_nll (abcd_span.hip) shares.  Every sum has a fixed
+// order: a frame's F columns in column order in fp32, the frames of a slice in
+// step order in fp64, the slices in slice order in fp64.  No atomics, no
+// device-global word, and no workgroup waits for another.
 #include <vector>
 
 #include "abcd_common.h"
+#include "abcd_emtile.h"
 #include "abcd_internal.h"
 #include "abcd_persist.h"
 #include "abcd_special.h"
 
 namespace abcd {
 
-constexpr int PW_TB = 32;      // segments per tile
-constexpr int PW_TP = 32;      // prototypes per tile
 constexpr int PW_TS = 16;      // steps per time slice: a constant, so a pair's order of sums depends on its length only
-constexpr int PW_FC = 64;      // columns staged per pass
-constexpr int PW_LD = PW_FC + 4;  // LDS row stride (16-byte aligned rows, staggered banks)
 constexpr int PW_MAX_T = 16383;   // T + 1 ints fit one slot of the pinned offset ring
 
-// the number of steps t with batch_sizes[t] = off[t + 1] - off[t] > b (batch_sizes is non-increasing)
-DEV int steps_longer(const int* __restrict__ off, int T, int b) {
-  int lo = 0, hi = T;  // the answer lies in [lo, hi]
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid + 1] - off[mid] > b) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
-// What one thread holds of the next staging pass while the current one is
-// computed: its 8 rows x 1 column of x, mu and log_var, and one offset logit or
-// target.
-struct PairRegs {
-  float x[PW_TB / 4], m[PW_TP / 4], l[PW_TP / 4], s;
-};
-
-// Workgroup (x: prototype tile, y: segment tile, z: time slice), 256 threads.
-// Per step the tile's 32 packed rows of x (contiguous: off[t] + b0 ...) and 32
-// prototype rows of mu / log_var (contiguous: t P + p0 ...) are staged in LDS,
-// 64 columns at a time, wave w taking rows w, w + 4, ... with its lanes on the
-// columns (coalesced).  e^-lv and 0.5 sum_f (log 2pi + lv) are formed there,
-// once per staged prototype element, so a pair costs a subtract, a multiply and
-// a fused multiply-add per column.  Thread (i, j) = (tid / 16, tid % 16) owns
-// segments b0 + 2 i, + 1 and prototypes p0 + j, + 16.  Rows with b >=
-// batch_sizes[t] (past the last step they lie beyond L) and prototypes >= P are
-// not read; columns >= F read as zero terms.
-//
-// The passes (step, column chunk) are pipelined inside the workgroup: the
-// global loads of pass i + 1 are issued into registers before pass i is
-// computed from LDS, and the two LDS images alternate, so one barrier per pass
-// orders everything (a thread writing image i + 1 has passed barrier i, which
-// every thread reaches only after computing pass i - 1 from that image).
+// Workgroup (x: prototype tile, y: segment tile, z: time slice), 256 threads,
+// over the emission tile of abcd_emtile.h (staging, pipelining, the 2 x 2
+// accumulation and the order of sums are described there).  What this kernel
+// adds: the tile's rows of x are the packed rows off[t] + b0 + r of step t
+// (contiguous), rows with b >= batch_sizes[t] (past the last step they lie
+// beyond L) are not read; want_em / want_off switch the two losses; a step's
+// offset logits and targets ride along its first pass (one value per thread of
+// waves 0 and 1) for the BCE; the frames of a slice join an fp64 sum in step
+// order, and the slice's partials go to its slab for pair_reduce.
 __global__ __launch_bounds__(256) void pair_nll(const float* __restrict__ X, const float* __restrict__ Y,
                                                 const float* __restrict__ MU, long ldm,
                                                 const float* __restrict__ LV, long ldl,
                                                 const float* __restrict__ OL, const int* __restrict__ off, int T,
                                                 int F, int B, int P, int want_em, int want_off,
                                                 double* __restrict__ part_em, double* __restrict__ part_off) {
-  __shared__ __attribute__((aligned(16))) float xs[2][PW_TB * PW_LD];
-  __shared__ __attribute__((aligned(16))) float ms[2][PW_TP * PW_LD];
-  __shared__ __attribute__((aligned(16))) float wsh[2][PW_TP * PW_LD];
-  __shared__ float cs[2][PW_TP], os[2][PW_TP], sps[2][PW_TP], ys[2][PW_TB];
+  __shared__ EmTile tile;
+  __shared__ float os[2][EM_TP], sps[2][EM_TP], ys[2][EM_TR];
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const int p0 = blockIdx.x * PW_TP, b0 = blockIdx.y * PW_TB, t0 = blockIdx.z * PW_TS;
+  const int p0 = blockIdx.x * EM_TP, b0 = blockIdx.y * EM_TR, t0 = blockIdx.z * PW_TS;
   const int len0 = steps_longer(off, T, b0);  // the tile's first segment is its longest
   if (t0 >= len0) return;                     // uniform: pair_reduce never reads this slice of this tile
   const int t1 = min(t0 + PW_TS, len0);
   const int ti = tid >> 4, tj = tid & 15;
-  const int nch = want_em ? (F + PW_FC - 1) / PW_FC : 1;  // passes per step
+  const int nch = want_em ? (F + EM_FC - 1) / EM_FC : 1;  // passes per step
   const int nit = (t1 - t0) * nch;
-  PairRegs g;
+  EmRegs g;
+  float gs;  // the next step's offset logit or target
   auto fetch = [&](int it) {
-    const int t = t0 + it / nch, c = it % nch, f = c * PW_FC + lane;
+    const int t = t0 + it / nch, c = it % nch, f = c * EM_FC + lane;
     const int o = off[t], nb = off[t + 1] - o;  // rows b < nb exist at this step
     if (want_em) {
-      const bool fin = f < F;
 #pragma unroll
-      for (int i = 0; i < PW_TB / 4; ++i) {
+      for (int i = 0; i < EM_TR / 4; ++i) {
         const int r = w + 4 * i;
-        g.x[i] = (fin && b0 + r < nb) ? X[(long)(o + b0 + r) * F + f] : 0.f;
+        g.x[i] = (f < F && b0 + r < nb) ? X[(long)(o + b0 + r) * F + f] : 0.f;
       }
-#pragma unroll
-      for (int i = 0; i < PW_TP / 4; ++i) {
-        const int r = w + 4 * i;
-        const bool ok = fin && p0 + r < P;
-        const long row = (long)t * P + p0 + r;
-        g.m[i] = ok ? MU[row * ldm + f] : 0.f;
-        g.l[i] = ok ? LV[row * ldl + f] : 0.f;
-      }
+      em_fetch_proto(g, MU, ldm, LV, ldl, w, t, p0, P, f, F);
     }
     if (want_off && c == 0) {
-      g.s = 0.f;
-      if (tid < PW_TP) {
-        if (p0 + tid < P) g.s = OL[(long)t * P + p0 + tid];
-      } else if (tid >= 64 && tid < 64 + PW_TB) {
-        if (b0 + tid - 64 < nb) g.s = Y[o + b0 + tid - 64];
+      gs = 0.f;
+      if (tid < EM_TP) {
+        if (p0 + tid < P) gs = OL[(long)t * P + p0 + tid];
+      } else if (tid >= 64 && tid < 64 + EM_TR) {
+        if (b0 + tid - 64 < nb) gs = Y[o + b0 + tid - 64];
       }
     }
   };
   double em[2][2] = {{0.0, 0.0}, {0.0, 0.0}}, bce[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
   float q[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-  float csum[PW_TP / 4];
-#pragma unroll
-  for (int i = 0; i < PW_TP / 4; ++i) csum[i] = 0.f;
+  float csum[EM_TP / 4] = {};
   fetch(0);
   for (int it = 0; it < nit; ++it) {
-    const int t = t0 + it / nch, c = it % nch, f0 = c * PW_FC, k = it & 1;
+    const int t = t0 + it / nch, c = it % nch, f0 = c * EM_FC, k = it & 1;
     const bool first = c == 0, last = c == nch - 1;
-    // ---- the fetched pass into LDS image k
-    if (want_em) {
-      const bool fin = f0 + lane < F;
-#pragma unroll
-      for (int i = 0; i < PW_TB / 4; ++i) xs[k][(w + 4 * i) * PW_LD + lane] = g.x[i];
-#pragma unroll
-      for (int i = 0; i < PW_TP / 4; ++i) {
-        const int r = w + 4 * i;
-        const bool ok = fin && p0 + r < P;
-        const float l = g.l[i];
-        ms[k][r * PW_LD + lane] = g.m[i];
-        wsh[k][r * PW_LD + lane] = ok ? __expf(-l) : 0.f;
-        const float cv = ok ? 1.8378770664093453f + l : 0.f;
-        csum[i] = first ? cv : csum[i] + cv;  // per lane: columns lane, lane + 64, ... in order
-      }
-      if (last) {  // the lanes' sums in a fixed tree
-#pragma unroll
-        for (int i = 0; i < PW_TP / 4; ++i) {
-          const float v = wave_sum(csum[i]);
-          if (lane == 0) cs[k][w + 4 * i] = 0.5f * v;
-        }
-      }
-    }
+    if (want_em) tile.stage(k, g, csum, w, lane, p0, P, f0, F, first, last);
     if (want_off && first) {
-      if (tid < PW_TP) {
-        os[k][tid] = g.s;
-        sps[k][tid] = log1pf(__expf(-fabsf(g.s)));
-      } else if (tid >= 64 && tid < 64 + PW_TB) {
-        ys[k][tid - 64] = g.s;
+      if (tid < EM_TP) {
+        os[k][tid] = gs;
+        sps[k][tid] = log1pf(__expf(-fabsf(gs)));
+      } else if (tid >= 64 && tid < 64 + EM_TR) {
+        ys[k][tid - 64] = gs;
       }
     }
     __syncthreads();
     if (it + 1 < nit) fetch(it + 1);  // in flight while this pass is computed
-    // ---- compute from image k
     const int nb = off[t + 1] - off[t];
     const bool v0 = b0 + 2 * ti < nb, v1 = b0 + 2 * ti + 1 < nb;
     if (want_em) {
-      if (first) q[0][0] = q[0][1] = q[1][0] = q[1][1] = 0.f;
-      const int n4 = (min(F - f0, PW_FC) + 3) >> 2;
-      const float4* x0 = (const float4*)(xs[k] + (2 * ti) * PW_LD);
-      const float4* x1 = (const float4*)(xs[k] + (2 * ti + 1) * PW_LD);
-      const float4* m0 = (const float4*)(ms[k] + tj * PW_LD);
-      const float4* m1 = (const float4*)(ms[k] + (tj + 16) * PW_LD);
-      const float4* w0 = (const float4*)(wsh[k] + tj * PW_LD);
-      const float4* w1 = (const float4*)(wsh[k] + (tj + 16) * PW_LD);
-#pragma unroll 2
-      for (int n = 0; n < n4; ++n) {
-        const float4 a0 = x0[n], a1 = x1[n], u0 = m0[n], u1 = m1[n], e0 = w0[n], e1 = w1[n];
-#define PW_TERM(Q, A, U, E)                                                          \
-  {                                                                                  \
-    float d = A.x - U.x; Q = fmaf(d * d, E.x, Q);                                    \
-    d = A.y - U.y; Q = fmaf(d * d, E.y, Q);                                          \
-    d = A.z - U.z; Q = fmaf(d * d, E.z, Q);                                          \
-    d = A.w - U.w; Q = fmaf(d * d, E.w, Q);                                          \
-  }
-        PW_TERM(q[0][0], a0, u0, e0)
-        PW_TERM(q[0][1], a0, u1, e1)
-        PW_TERM(q[1][0], a1, u0, e0)
-        PW_TERM(q[1][1], a1, u1, e1)
-#undef PW_TERM
-      }
+      tile.accumulate(k, q, ti, tj, f0, F, first);
       if (last) {  // the frame is complete: one fp32 value per pair joins the fp64 sum
-        const float c0 = cs[k][tj], c1 = cs[k][tj + 16];
+        const float c0 = tile.cs[k][tj], c1 = tile.cs[k][tj + 16];
         if (v0) {
           em[0][0] += (double)(c0 + 0.5f * q[0][0]);
           em[0][1] += (double)(c1 + 0.5f * q[0][1]);
@@ -234,7 +152,7 @@ __global__ __launch_bounds__(256) void pair_reduce(const double* __restrict__ pa
   const long at = (long)blockIdx.x * 256 + threadIdx.x;
   if (at >= (long)B * P) return;
   const int b = (int)(at / P), p = (int)(at - (long)b * P);
-  const int ns = (steps_longer(off, T, b / PW_TB * PW_TB) + PW_TS - 1) / PW_TS;
+  const int ns = (steps_longer(off, T, b / EM_TR * EM_TR) + PW_TS - 1) / PW_TS;
   const size_t slab = (size_t)B * (size_t)P;
   if (pair_em) {
     double s = 0.0;
@@ -272,11 +190,7 @@ __global__ __launch_bounds__(256) void pair_posterior(const float* __restrict__ 
     const double s = score(p);
     if (s > m) { m = s; arg = p; }  // ascending p per lane: the lowest index of the lane's maximum
   }
-  for (int o = 32; o > 0; o >>= 1) {
-    const double m2 = __shfl_xor(m, o, 64);
-    const int a2 = __shfl_xor(arg, o, 64);
-    if (m2 > m || (m2 == m && a2 < arg)) { m = m2; arg = a2; }
-  }
+  wave_argmax(m, arg);
   const bool none = !(m > -INFINITY);
   double se = 0.0;
   if (!none)
@@ -327,16 +241,15 @@ extern "C" int abcd_pairwise_nll(const abcd_packed* x, const float* gt_offset, i
   if (!pair_em && !pair_off) return 0;
   hipStream_t s = (hipStream_t)stream;
   const int T = x->T, B = x->B;
-  std::vector<int> off((size_t)T + 1, 0);
-  for (int t = 0; t < T; ++t) off[t + 1] = off[t] + (int)x->batch_sizes[t];
+  const std::vector<int> off = step_offsets(x->batch_sizes, T);
   int* doff = (int*)ws;
   const size_t offb = (((size_t)T + 1) * sizeof(int) + 255) & ~(size_t)255;
   const int ns = cdiv(T, PW_TS);
   double* part_em = (double*)((char*)ws + offb);
   double* part_off = part_em + (size_t)ns * B * P;
   ABCD_TRY((hipError_t)upload_offsets(s, off, doff));  // pinned ring + async copy: no host synchronisation
-  const dim3 grid(cdiv(P, PW_TP), cdiv(B, PW_TB), ns);
-  note_dispatch(TK_PAIR_NLL, "pair_nll<%dx%dx%d> grid %dx%dx%d", PW_TB, PW_TP, PW_TS, grid.x, grid.y, grid.z);
+  const dim3 grid(cdiv(P, EM_TP), cdiv(B, EM_TR), ns);
+  note_dispatch(TK_PAIR_NLL, "pair_nll<%dx%dx%d> grid %dx%dx%d", EM_TR, EM_TP, PW_TS, grid.x, grid.y, grid.z);
   {
     TimedScope ts(s, TK_PAIR_NLL);
     pair_nll<<<grid, 256, 0, s>>>(x->data, gt_offset, proto_mu, ld_mu, proto_lv, ld_lv, proto_offset_logits, doff, T,

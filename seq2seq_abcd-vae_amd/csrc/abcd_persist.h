@@ -124,6 +124,12 @@ inline size_t persist_part_floats(int nd, int B, int H) {
 // of the 64-row layouts
 inline size_t persist_sync_uints(int nd, int B) { return (size_t)(66 * nd * cdiv(B, 32) + 9) * PERSIST_SYNC_STRIDE; }
 
+// off[0..T] of the packed layout: off[t + 1] = off[t] + batch_sizes[t]
+inline std::vector<int> step_offsets(const int64_t* bs, int T) {
+  std::vector<int> off((size_t)T + 1, 0);
+  for (int t = 0; t < T; ++t) off[t + 1] = off[t] + (int)bs[t];
+  return off;
+}
 // Copy off[0..T] to device memory `dst` on stream s through a pinned ring
 // (asynchronous, no host/device synchronisation).
 int upload_offsets(hipStream_t s, const std::vector<int>& off, int* dst);

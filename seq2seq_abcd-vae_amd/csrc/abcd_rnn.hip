@@ -38,12 +38,6 @@ int validate_batch(const int64_t* bs, int T, int L, int B) {
   return s == L ? 0 : ABCD_EINVAL;
 }
 
-static std::vector<int> step_offsets(const int64_t* bs, int T) {
-  std::vector<int> off(T + 1, 0);
-  for (int t = 0; t < T; ++t) off[t + 1] = off[t] + (int)bs[t];
-  return off;
-}
-
 // ===========================================================================
 // forward step: gates = [x-part] + Hprev_rows @ W_hh^T, cell update epilogue
 // ===========================================================================

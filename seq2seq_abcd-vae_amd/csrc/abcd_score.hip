@@ -203,8 +203,7 @@ extern "C" int abcd_segment_losses(const abcd_packed* x, const float* mu, long l
   ABCD_REQUIRE(ws && ws_bytes >= abcd_segment_losses_workspace_bytes(x->T, x->B));
   if (!seg_em && !seg_off && !seg_len) return 0;
   hipStream_t s = (hipStream_t)stream;
-  std::vector<int> off((size_t)x->T + 1, 0);
-  for (int t = 0; t < x->T; ++t) off[t + 1] = off[t] + (int)x->batch_sizes[t];
+  const std::vector<int> off = step_offsets(x->batch_sizes, x->T);
   int* doff = (int*)ws;
   ABCD_TRY((hipError_t)upload_offsets(s, off, doff));  // pinned ring + async copy: no host synchronisation
   note_dispatch(TK_SEG_LOSSES, "seg_losses<%d> grid %d", 64 * SEG_WAVES, x->B);

@@ -14,23 +14,20 @@
 //   span_viterbi  one workgroup: the semi-Markov dynamic programme over the
 //                 output of span_nll and the backtrack
 //
-// span_nll is pair_nll's sliding-window sibling: the same staging, the same
-// per-term expressions and the same order of sums (a frame's F columns in
-// column order in fp32, frames in step order in fp64), with the frame of start
-// s at step t being row s + t of the recording.  No atomics, no device-global
-// word, and no workgroup waits for another.
+// span_nll runs on the emission tile pair_nll runs on (abcd_emtile.h: the
+// staging, the per-term expressions and the order of a frame's sums, F columns
+// in column order in fp32), with the frame of start s at step t being row s + t
+// of the recording; frames join in step order in fp64.  No atomics, no
+// device-global word, and no workgroup waits for another.
 #include <climits>
 
 #include "abcd_common.h"
+#include "abcd_emtile.h"
 #include "abcd_internal.h"
 #include "abcd_special.h"
 
 namespace abcd {
 
-constexpr int SP_TS = 32;      // starts per tile
-constexpr int SP_TP = 32;      // prototypes per tile
-constexpr int SP_FC = 64;      // columns staged per pass
-constexpr int SP_LD = SP_FC + 4;  // LDS row stride (16-byte aligned rows, staggered banks)
 constexpr int SP_MAX_D = 16383;
 
 DEV double softplus_d(double v) { return fmax(v, 0.0) + log1p(exp(-fabs(v))); }
@@ -61,125 +58,57 @@ __global__ __launch_bounds__(256) void span_fill(long rows, int D, double* __res
   span_cat[e * lds + c] = -1;
 }
 
-// What one thread holds of the next staging pass while the current one is
-// computed: its 8 rows x 1 column of x, mu and log_var.
-struct SpanRegs {
-  float x[SP_TS / 4], m[SP_TP / 4], l[SP_TP / 4];
-};
-
 // Workgroup blockIdx.x owns starts s0 = 32 blockIdx.x .. s0 + 31 and every
 // output entry (e = s + d, d) of theirs, so it max-combines the prototype tiles
-// itself, in tile order.  Per step t the 32 frame rows s0 + t .. s0 + t + 31
-// and the 32 prototype rows t P + p0 .. are staged, 64 columns at a time, as
-// pair_nll stages them (wave w takes rows w, w + 4, ... with its lanes on the
-// columns; e^-lv and 0.5 sum_f (log 2pi + lv) are formed once per staged
-// prototype element; the loads of pass i + 1 are in flight while pass i is
-// computed, two LDS images alternate, one barrier per pass).  Thread (i, j) =
-// (tid / 16, tid % 16) owns starts s0 + 2 i, + 1 and prototypes p0 + j, + 16.
-// After a step's last column chunk the 16 lanes that hold one start's 32
-// prototypes reduce (score, index) by shuffles, the lowest index winning a tie,
-// and lane j = 0 folds the result into the output entry: a plain store for the
-// first prototype tile, a read and a strict comparison for the later ones (the
-// same thread wrote what it reads).  Rows >= N, steps >= D, prototypes >= P
-// and columns >= F are not read.
+// itself, in tile order, each over the emission tile of abcd_emtile.h (staging,
+// pipelining, the 2 x 2 accumulation and the order of sums are described
+// there).  What this kernel adds: the tile's rows of x at step t are the frame
+// rows s0 + t .. s0 + t + 31 of the recording, so thread (i, j) owns starts
+// s0 + 2 i, + 1; the frames of a start join an fp64 sum in step order.  After
+// a step's last column chunk the 16 lanes that hold one start's 32 prototypes
+// reduce (score, index), the lowest index winning a tie, and lane j = 0 folds
+// the result into the output entry: a plain store for the first prototype
+// tile, a read and a strict comparison for the later ones (the same thread
+// wrote what it reads).  Rows >= N and steps >= D are not read.
 __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, long ldx, long N, int F, int P, int D,
                                                 const float* __restrict__ MU, long ldm,
                                                 const float* __restrict__ LV, long ldl,
                                                 const double* __restrict__ Otab, const float* __restrict__ LW,
                                                 double* __restrict__ span_score, int32_t* __restrict__ span_cat,
                                                 long lds) {
-  __shared__ __attribute__((aligned(16))) float xs[2][SP_TS * SP_LD];
-  __shared__ __attribute__((aligned(16))) float ms[2][SP_TP * SP_LD];
-  __shared__ __attribute__((aligned(16))) float wsh[2][SP_TP * SP_LD];
-  __shared__ float cs[2][SP_TP];
+  __shared__ EmTile tile;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-  const long s0 = (long)blockIdx.x * SP_TS;
+  const long s0 = (long)blockIdx.x * EM_TR;
   const int nst = (int)min((long)D, N - s0);  // the tile's first start has the most steps
   const int ti = tid >> 4, tj = tid & 15;
-  const int nch = (F + SP_FC - 1) / SP_FC;  // passes per step
+  const int nch = (F + EM_FC - 1) / EM_FC;  // passes per step
   const int nit = nst * nch;
-  for (int p0 = 0; p0 < P; p0 += SP_TP) {
-    SpanRegs g;
+  for (int p0 = 0; p0 < P; p0 += EM_TP) {
+    EmRegs g;
     auto fetch = [&](int it) {
-      const int t = it / nch, c = it % nch, f = c * SP_FC + lane;
-      const bool fin = f < F;
+      const int t = it / nch, c = it % nch, f = c * EM_FC + lane;
 #pragma unroll
-      for (int i = 0; i < SP_TS / 4; ++i) {
+      for (int i = 0; i < EM_TR / 4; ++i) {
         const long row = s0 + t + w + 4 * i;
-        g.x[i] = (fin && row < N) ? X[row * ldx + f] : 0.f;
+        g.x[i] = (f < F && row < N) ? X[row * ldx + f] : 0.f;
       }
-#pragma unroll
-      for (int i = 0; i < SP_TP / 4; ++i) {
-        const int r = w + 4 * i;
-        const bool ok = fin && p0 + r < P;
-        const long row = (long)t * P + p0 + r;
-        g.m[i] = ok ? MU[row * ldm + f] : 0.f;
-        g.l[i] = ok ? LV[row * ldl + f] : 0.f;
-      }
+      em_fetch_proto(g, MU, ldm, LV, ldl, w, t, p0, P, f, F);
     };
     const int pa = p0 + tj, pb = p0 + tj + 16;
     const double lwa = (pa < P && LW) ? (double)LW[pa] : 0.0, lwb = (pb < P && LW) ? (double)LW[pb] : 0.0;
     double em[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
     float q[2][2] = {{0.f, 0.f}, {0.f, 0.f}};
-    float csum[SP_TP / 4];
-#pragma unroll
-    for (int i = 0; i < SP_TP / 4; ++i) csum[i] = 0.f;
+    float csum[EM_TP / 4] = {};
     fetch(0);
     for (int it = 0; it < nit; ++it) {
-      const int t = it / nch, c = it % nch, f0 = c * SP_FC, k = it & 1;
+      const int t = it / nch, c = it % nch, f0 = c * EM_FC, k = it & 1;
       const bool first = c == 0, last = c == nch - 1;
-      // ---- the fetched pass into LDS image k
-      {
-        const bool fin = f0 + lane < F;
-#pragma unroll
-        for (int i = 0; i < SP_TS / 4; ++i) xs[k][(w + 4 * i) * SP_LD + lane] = g.x[i];
-#pragma unroll
-        for (int i = 0; i < SP_TP / 4; ++i) {
-          const int r = w + 4 * i;
-          const bool ok = fin && p0 + r < P;
-          const float l = g.l[i];
-          ms[k][r * SP_LD + lane] = g.m[i];
-          wsh[k][r * SP_LD + lane] = ok ? __expf(-l) : 0.f;
-          const float cv = ok ? 1.8378770664093453f + l : 0.f;
-          csum[i] = first ? cv : csum[i] + cv;  // per lane: columns lane, lane + 64, ... in order
-        }
-        if (last) {  // the lanes' sums in a fixed tree
-#pragma unroll
-          for (int i = 0; i < SP_TP / 4; ++i) {
-            const float v = wave_sum(csum[i]);
-            if (lane == 0) cs[k][w + 4 * i] = 0.5f * v;
-          }
-        }
-      }
+      tile.stage(k, g, csum, w, lane, p0, P, f0, F, first, last);
       __syncthreads();
       if (it + 1 < nit) fetch(it + 1);  // in flight while this pass is computed
-      // ---- compute from image k
-      if (first) q[0][0] = q[0][1] = q[1][0] = q[1][1] = 0.f;
-      const int n4 = (min(F - f0, SP_FC) + 3) >> 2;
-      const float4* x0 = (const float4*)(xs[k] + (2 * ti) * SP_LD);
-      const float4* x1 = (const float4*)(xs[k] + (2 * ti + 1) * SP_LD);
-      const float4* m0 = (const float4*)(ms[k] + tj * SP_LD);
-      const float4* m1 = (const float4*)(ms[k] + (tj + 16) * SP_LD);
-      const float4* w0 = (const float4*)(wsh[k] + tj * SP_LD);
-      const float4* w1 = (const float4*)(wsh[k] + (tj + 16) * SP_LD);
-#pragma unroll 2
-      for (int n = 0; n < n4; ++n) {
-        const float4 a0 = x0[n], a1 = x1[n], u0 = m0[n], u1 = m1[n], e0 = w0[n], e1 = w1[n];
-#define SP_TERM(Q, A, U, E)                                                          \
-  {                                                                                  \
-    float d = A.x - U.x; Q = fmaf(d * d, E.x, Q);                                    \
-    d = A.y - U.y; Q = fmaf(d * d, E.y, Q);                                          \
-    d = A.z - U.z; Q = fmaf(d * d, E.z, Q);                                          \
-    d = A.w - U.w; Q = fmaf(d * d, E.w, Q);                                          \
-  }
-        SP_TERM(q[0][0], a0, u0, e0)
-        SP_TERM(q[0][1], a0, u1, e1)
-        SP_TERM(q[1][0], a1, u0, e0)
-        SP_TERM(q[1][1], a1, u1, e1)
-#undef SP_TERM
-      }
+      tile.accumulate(k, q, ti, tj, f0, F, first);
       if (last) {  // the frame is complete: one fp32 value per (start, prototype) joins the fp64 sum
-        const float c0 = cs[k][tj], c1 = cs[k][tj + 16];
+        const float c0 = tile.cs[k][tj], c1 = tile.cs[k][tj + 16];
         const double oa = pa < P ? Otab[(long)t * P + pa] : 0.0, ob = pb < P ? Otab[(long)t * P + pb] : 0.0;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -195,14 +124,7 @@ __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, lon
           if (!(sa > -INFINITY)) { sa = -INFINITY; arg = INT_MAX; }  // NaN and -inf: excluded
           if (!(sb > -INFINITY)) { sb = -INFINITY; ab = INT_MAX; }
           if (sb > sa) { sa = sb; arg = ab; }
-#pragma unroll
-          for (int o = 8; o > 0; o >>= 1) {  // the 16 lanes of one start
-            const double s2 = __shfl_xor(sa, o, 64);
-            const int a2 = __shfl_xor(arg, o, 64);
-            const bool take = (s2 > sa) | ((s2 == sa) & (a2 < arg));  // no short-circuit: selects, not branches
-            sa = take ? s2 : sa;
-            arg = take ? a2 : arg;
-          }
+          wave_argmax<16>(sa, arg);  // the 16 lanes of one start
           if (tj == 0 && v) {
             const long at = e * lds + t;
             if (p0 == 0) {
@@ -298,13 +220,7 @@ __global__ __launch_bounds__(SV_THREADS) void span_viterbi(const double* __restr
       const double c = ring[at] + SS[n * lds + d - 1];
       if (c > best) { best = c; bd = d; }
     }
-    for (int o = 32; o > 0; o >>= 1) {
-      const double b2 = __shfl_xor(best, o, 64);
-      const int d2 = __shfl_xor(bd, o, 64);
-      const bool take = (b2 > best) | ((b2 == best) & (d2 < bd));  // no short-circuit: selects, not branches
-      best = take ? b2 : best;
-      bd = take ? d2 : bd;
-    }
+    wave_argmax(best, bd);
     const int k = (int)(n & 1);
     if (lane == 0) { wb[k][w] = best; wd[k][w] = bd; }
     __syncthreads();
@@ -384,7 +300,7 @@ extern "C" int abcd_span_scores(const float* x, long ld_x, long N, int F, int P,
   if (N == 0) return 0;
   double* Otab = (double*)ws;
   span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<<<cdiv(N, SP_TS), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab, log_weight,
+  span_nll<<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab, log_weight,
                                           span_score, span_cat, ld_span);
   ABCD_CHECK_LAUNCH();
   return 0;

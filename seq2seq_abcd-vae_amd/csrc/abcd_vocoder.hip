@@ -62,22 +62,12 @@ struct GlArgs {
   float eps, norm, alpha;
 };
 
-// the number of steps t with batch_sizes[t] = off[t + 1] - off[t] > b (batch_sizes is non-increasing)
-DEV int gl_frames(const int* __restrict__ off, int T, int b) {
-  int lo = 0, hi = T;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (off[mid + 1] - off[mid] > b) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-
 template <bool LDS>
 __global__ __launch_bounds__(GL_THREADS) void griffin_lim(GlArgs a) {
   extern __shared__ __attribute__((aligned(16))) float gsm[];
   const int n = a.n, hop = a.hop, F = a.F, tid = threadIdx.x, b = blockIdx.x;
   const int nthr = blockDim.x;  // 1024, or what ABCD_GL_WAVES asks for
-  const int Tb = gl_frames(a.off, a.T, b);
+  const int Tb = steps_longer(a.off, a.T, b);  // this segment's frames
   const int pad = n / 2, rpad = n - pad;
   const int S = hop * (Tb - 1);
   float* wrow = a.wave + (long)b * a.ldw;
@@ -374,8 +364,7 @@ extern "C" int abcd_griffin_lim(const float* logamp, int ld, const int64_t* batc
   const int smax = abcd_griffin_lim_samples(T, n_fft, hop, 1);
   ABCD_REQUIRE(ldw >= smax && ldw >= 1);
   hipStream_t s = (hipStream_t)stream;
-  std::vector<int> off((size_t)T + 1, 0);
-  for (int t = 0; t < T; ++t) off[t + 1] = off[t] + (int)batch_sizes[t];
+  const std::vector<int> off = step_offsets(batch_sizes, T);
   char* base = (char*)ws;
   int* doff = (int*)base;
   float2* C = (float2*)(base + p.off_bytes);

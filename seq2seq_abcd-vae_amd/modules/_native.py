@@ -253,8 +253,7 @@ def source_hash():
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     names = ["abcd_gemm.hip", "abcd_rnn.hip", "abcd_persist.hip", "abcd_sampler.hip", "abcd_optim.hip",
              "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_vocoder.hip", "abcd_chain.hip", "abcd_span.hip",
-             "abcd_common.h",
-             "abcd_internal.h",
+             "abcd_common.h", "abcd_emtile.h", "abcd_internal.h",
              "abcd_persist.h", "abcd_special.h", "abcd_x6.h", "../../include/abcd_hip.h"]
     h = hashlib.sha256()
     for n in sorted(names):
@@ -343,6 +342,24 @@ def require_gpu(t):
 
 def ptr(t):
     return None if t is None else c_void_p(t.data_ptr())
+
+
+def packed(data, batch_sizes, F, L=None):
+    """-> (abcd_packed struct, the host int64 batch_sizes it points at: keep it
+    alive while the struct is used).  data may be None (a null data pointer);
+    then L is the given one, else batch_sizes' sum."""
+    bs = batch_sizes
+    if bs.dtype != torch.int64 or bs.device.type != "cpu":
+        bs = bs.to("cpu", torch.int64)
+    bs = bs.contiguous()
+    st = Packed()
+    st.data = data.data_ptr() if data is not None else None
+    st.batch_sizes = bs.data_ptr()
+    st.T = int(bs.numel())
+    st.L = int(data.shape[0]) if data is not None else int(bs.sum()) if L is None else int(L)
+    st.B = int(bs[0])
+    st.F = int(F)
+    return st, bs
 
 
 def stream():

@@ -155,7 +155,7 @@ class FusedStep:
         st = N.stream()
         data = data.contiguous()
         N.require_gpu(data)
-        pk, bs_keep = _packed(data, batch_sizes, self.enc_cfg.input_size)
+        pk, bs_keep = N.packed(data, batch_sizes, self.enc_cfg.input_size)
         T, L, B = pk.T, pk.L, pk.B
         Bn = int(loss_batch) if loss_batch is not None else B
         dev = self.device
@@ -431,18 +431,3 @@ class StatusWatch:
 
     def finish(self):
         self._read()
-
-
-def _packed(data, batch_sizes, F):
-    bs = batch_sizes
-    if bs.dtype != torch.int64 or bs.device.type != "cpu":
-        bs = bs.to("cpu", torch.int64)
-    bs = bs.contiguous()
-    st = N.Packed()
-    st.data = data.data_ptr()
-    st.batch_sizes = bs.data_ptr()
-    st.T = int(bs.numel())
-    st.L = int(data.shape[0])
-    st.B = int(bs[0])
-    st.F = int(F)
-    return st, bs

@@ -57,21 +57,6 @@ def log_pdf_isotropic_gaussian(value, mean, log_variance):
     return -0.5 * (math.log(2 * math.pi) + log_variance + d * (-log_variance).exp() * d).sum()
 
 
-def _packed_struct(data, batch_sizes, F):
-    bs = batch_sizes
-    if bs.dtype != torch.int64 or bs.device.type != "cpu":
-        bs = bs.to("cpu", torch.int64)
-    bs = bs.contiguous()
-    st = N.Packed()
-    st.data = data.data_ptr() if data is not None else None
-    st.batch_sizes = bs.data_ptr()
-    st.T = int(bs.numel())
-    st.L = int(data.shape[0]) if data is not None else int(bs.sum())
-    st.B = int(bs[0])
-    st.F = int(F)
-    return st, bs  # keep bs alive while the struct is used
-
-
 def _f32c(t):
     if t.dtype != torch.float32:
         raise TypeError(f"fp32 tensors only (got {t.dtype})")

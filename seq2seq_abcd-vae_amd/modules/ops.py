@@ -65,21 +65,6 @@ def _u64(x):
     return int(x) & _U64
 
 
-def _packed(data, batch_sizes, F, L=None):
-    bs = batch_sizes
-    if bs.dtype != torch.int64 or bs.device.type != "cpu":
-        bs = bs.to("cpu", torch.int64)
-    bs = bs.contiguous()
-    st = N.Packed()
-    st.data = data.data_ptr() if data is not None else None
-    st.batch_sizes = bs.data_ptr()
-    st.T = int(bs.numel())
-    st.L = int(data.shape[0]) if data is not None else int(bs.sum()) if L is None else int(L)
-    st.B = int(bs[0])
-    st.F = int(F)
-    return st, bs
-
-
 def _ptrs(ts):
     return [None if t is None else t.data_ptr() for t in ts]
 
@@ -116,7 +101,7 @@ def encoder(data: Tensor, batch_sizes: Tensor, weights: List[Tensor], noise: Lis
     N.require_gpu(data)
     L = N.lib()
     c = _enc_cfg(cfg)
-    pk, bs = _packed(data, batch_sizes, cfg[0])
+    pk, bs = N.packed(data, batch_sizes, cfg[0])
     nbytes = L.abcd_encoder_workspace_bytes(c, pk.T, pk.L, pk.B)
     if nbytes == 0:
         raise N.HipError("encoder: unsupported configuration (hidden size must be a multiple of 16)")
@@ -138,7 +123,7 @@ def _(data, batch_sizes, weights, noise, cfg):
 def encoder_bwd(data: Tensor, batch_sizes: Tensor, weights: List[Tensor], noise: List[Tensor],
                 ws: Tensor, d_out: Tensor, cfg: List[int]) -> List[Tensor]:
     c = _enc_cfg(cfg)
-    pk, bs = _packed(data, batch_sizes, cfg[0])
+    pk, bs = N.packed(data, batch_sizes, cfg[0])
     grads = [torch.empty_like(w) for w in weights]
     N.check(N.lib().abcd_encoder_backward_dropout(c, _enc_struct(cfg, weights), pk, N.ptr_array(list(noise) or None),
                                                   N.ptr(d_out.contiguous()), _enc_struct(cfg, grads), N.ptr(ws),
@@ -400,7 +385,7 @@ def decoder(features: Tensor, batch_sizes: Tensor, speaker: Optional[Tensor], gt
     L_ = N.lib()
     c = _dec_cfg(cfg)
     F = int(cfg[0])
-    pk, bs = _packed(gt, batch_sizes, F)
+    pk, bs = N.packed(gt, batch_sizes, F)
     nbytes = L_.abcd_decoder_workspace_bytes(c, pk.T, pk.L, pk.B)
     if nbytes == 0:
         raise N.HipError("decoder: unsupported configuration (sizes must be multiples of 16)")
@@ -435,7 +420,7 @@ def decoder_bwd(features: Tensor, batch_sizes: Tensor, speaker: Optional[Tensor]
                 cfg: List[int]) -> List[Tensor]:
     """-> [d_features, d_params...]"""
     c = _dec_cfg(cfg)
-    pk, bs = _packed(gt, batch_sizes, int(cfg[0]))
+    pk, bs = N.packed(gt, batch_sizes, int(cfg[0]))
     dev = features.device
     spk = speaker.to(dev, torch.int64).contiguous() if int(cfg[6]) else None
     grads = [torch.empty_like(p) for p in params]
@@ -561,6 +546,14 @@ def _forward_only(op, name):
     op.register_autograd(backward, setup_context=setup)
 
 
+def _rows(t):
+    """(tensor, row stride): a row-strided 2-d view passes as it is; anything else is made contiguous."""
+    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
+        return t, t.stride(0)
+    t = t.contiguous()
+    return t, t.shape[1]
+
+
 @torch.library.custom_op("abcd::segment_losses", mutates_args=())
 def segment_losses(gt: Optional[Tensor], batch_sizes: Tensor, mu: Optional[Tensor], log_var: Optional[Tensor],
                    offset_logits: Optional[Tensor], gt_offset: Optional[Tensor], F: int) -> List[Tensor]:
@@ -577,17 +570,11 @@ def segment_losses(gt: Optional[Tensor], batch_sizes: Tensor, mu: Optional[Tenso
     want_em = gt is not None and mu is not None and log_var is not None
     want_off = offset_logits is not None and gt_offset is not None
     gt = gt.contiguous() if want_em else None
-
-    def rows(t):  # a row-strided L x F view passes as it is; anything else is made contiguous
-        if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
-            return t, t.stride(0)
-        t = t.contiguous()
-        return t, t.shape[1]
-    (mu, ldm), (log_var, ldl) = (rows(mu), rows(log_var)) if want_em else ((None, 0), (None, 0))
+    (mu, ldm), (log_var, ldl) = (_rows(mu), _rows(log_var)) if want_em else ((None, 0), (None, 0))
     offset_logits = offset_logits.contiguous() if want_off else None
     gt_offset = gt_offset.contiguous() if want_off else None
     L_ = N.lib()
-    pk, bs = _packed(gt, batch_sizes, F)
+    pk, bs = N.packed(gt, batch_sizes, F)
     if want_em and not (tuple(mu.shape) == tuple(log_var.shape) == (pk.L, int(F)) and gt.shape[1] == int(F)):
         raise ValueError(f"segment_losses: gt, mu and log_var must be {(pk.L, int(F))}")
     if want_off and not (offset_logits.numel() == gt_offset.numel() == pk.L):
@@ -643,14 +630,6 @@ def _(logits, psl, cfg, prior, entire_data_size):
 _forward_only(sampler_kl_rows, "sampler_kl_rows")
 
 
-def _rows(t):
-    """(tensor, row stride): a row-strided 2-d view passes as it is; anything else is made contiguous."""
-    if t.dim() == 2 and t.stride(1) == 1 and t.stride(0) >= t.shape[1]:
-        return t, t.stride(0)
-    t = t.contiguous()
-    return t, t.shape[1]
-
-
 @torch.library.custom_op("abcd::pairwise_nll", mutates_args=())
 def pairwise_nll(gt: Optional[Tensor], batch_sizes: Tensor, gt_offset: Optional[Tensor], proto_mu: Optional[Tensor],
                  proto_lv: Optional[Tensor], proto_offset_logits: Optional[Tensor], P: int, F: int) -> List[Tensor]:
@@ -680,7 +659,7 @@ def pairwise_nll(gt: Optional[Tensor], batch_sizes: Tensor, gt_offset: Optional[
     ol = proto_offset_logits.contiguous() if want_off else None
     gt_offset = gt_offset.contiguous() if want_off else None
     L_ = N.lib()
-    pk, bs = _packed(gt, batch_sizes, F)
+    pk, bs = N.packed(gt, batch_sizes, F)
     rows = mu.shape[0] if want_em else ol.numel()
     if rows % P or rows // P < pk.T:
         raise ValueError(f"pairwise_nll: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {pk.T}, "
@@ -1000,7 +979,7 @@ def griffin_lim(logamp: Tensor, batch_sizes: Tensor, window: Tensor, phase0: Ten
     (x, ld), (ph, ldp) = _rows(logamp.float()), _rows(phase0.float())
     win = window.float().contiguous()
     L_ = N.lib()
-    pk, bs = _packed(x, batch_sizes, F)
+    pk, bs = N.packed(x, batch_sizes, F)
     smax = int(L_.abcd_griffin_lim_samples(pk.T, n_fft, int(hop), 1))
     nbytes = L_.abcd_griffin_lim_workspace_bytes(pk.B, pk.T, n_fft, int(hop))
     if nbytes == 0:
