@@ -37,9 +37,10 @@ import os
 import numpy as np
 import torch
 
+import cli
 import score
-from modules import _native, data_utils, ops
-from modules.data_utils import Compose
+from cli import PRIORS
+from modules import _native, ops
 
 COLUMNS = ("data_ix", "length", "category_ix", "category_prob", "decoder_category_ix", "decoder_category_prob",
            "log_evidence", "agree")
@@ -49,7 +50,6 @@ TABLE = (("length", np.int64), ("category_ix", np.int64), ("category_prob", np.f
 MATRIX_COLUMNS = ("data_ix", "category_ix", "emission_nll", "end_prediction_loss", "log_weight", "responsibility")
 MATRIX = (("category_ix", np.int64), ("emission_nll", np.float64), ("end_prediction_loss", np.float64),
           ("log_weight", np.float64), ("responsibility", np.float64))
-PRIORS = ("dirichlet", "uniform")
 
 
 class Classifier(score.Scorer):
@@ -134,30 +134,16 @@ def get_parameters(argv=None):
     import argparse
     p = argparse.ArgumentParser(description="Score annotated segments against every category of a trained ABCD-VAE "
                                             "(MI355X): decoder-side classification, responsibilities and evidence.")
-    p.add_argument("model_path", type=str, help="checkpoint.pt written by learning.py (this package or the reference)")
-    p.add_argument("input_root", type=str, help="directory the annotation's wav paths are relative to")
-    p.add_argument("annotation_file", type=str, help="annotation table (csv) of the segments to classify")
-    p.add_argument("data_normalizer", type=float, help="log-amplitudes are divided by this (training's -N)")
-    p.add_argument("--annotation_sep", type=str, default=",", help="field separator of the annotation table")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
-    p.add_argument("-S", "--save_path", type=str, default=None,
-                   help="output csv (default: <input_root>/classified.csv); an existing file is kept as .prev")
-    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
-    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
-    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
-    p.add_argument("--fft_no_centering", action="store_true", help="STFT without centre padding")
-    p.add_argument("--channel", type=int, default=0, help="channel (0-based) of multi-channel wav files")
-    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
-    p.add_argument("-b", "--batch_size", type=int, default=1, help="segments per forward pass")
-    p.add_argument("--prior", type=str, default="dirichlet", choices=PRIORS,
-                   help="log weights of the categories: the Dirichlet posterior's E[log pi_k] (default) or zero")
-    p.add_argument("--entire_data_size", type=float, default=None,
-                   help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the number of segments)")
+    cli.add_data_arguments(p, table_help="annotation table (csv) of the segments to classify",
+                           save_help="output csv (default: <input_root>/classified.csv); an existing file is kept as "
+                                     ".prev")
+    cli.add_prior_arguments(
+        p, prior_help="log weights of the categories: the Dirichlet posterior's E[log pi_k] (default) or zero",
+        size_help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the number of segments)")
     p.add_argument("--matrix", type=str, default=None,
                    help="also write the long table of every (segment, category) to this csv")
     a = p.parse_args(argv)
-    if a.entire_data_size is not None and not a.entire_data_size > 0:
-        p.error("--entire_data_size must be positive")
+    cli.check_prior_arguments(p, a)
     return a
 
 
@@ -167,16 +153,10 @@ def main(argv=None):
     for path in (save_path, a.matrix):
         if path and os.path.dirname(path):
             os.makedirs(os.path.dirname(path), exist_ok=True)
-    parser = data_utils.Data_Parser(a.input_root, a.annotation_file, annotation_sep=a.annotation_sep)
-    fs = parser.get_sample_freq()
-    frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))
-    clf = Classifier(a.model_path, device=a.device)
-    eps, norm = a.epsilon, a.data_normalizer
-    tfm = Compose([data_utils.ToTensor(),
-                   data_utils.STFT(frame, hop, window=a.fft_window_type, centering=not a.fft_no_centering),
-                   data_utils.Transform(lambda x: (x + eps).log() / norm)])
-    clf.classify_dataset(parser.get_data(transform=tfm, channel=a.channel), save_path, batch_size=a.batch_size,
-                         prior=a.prior, entire_data_size=a.entire_data_size, matrix_path=a.matrix)
+    dataset = cli.open_dataset(a)
+    Classifier(a.model_path, device=a.device).classify_dataset(
+        dataset, save_path, batch_size=a.batch_size, prior=a.prior, entire_data_size=a.entire_data_size,
+        matrix_path=a.matrix)
     return save_path
 
 

@@ -23,26 +23,16 @@ import os
 import numpy as np
 import torch
 
+import cli
 import learning
-from encode import rename_existing_file
 from modules import _native, noise
 
 
-class Decoder(learning.Learner):
+class Decoder(cli.FrozenCheckpoint, learning.Learner):
     """A trained ABCD checkpoint (ours or the reference's) opened for
     generation: parameters frozen, modules in eval mode."""
-
-    def __init__(self, model_config_path, device="cuda"):
-        self.device = torch.device(device)
-        ckpt = torch.load(model_config_path, map_location="cpu", weights_only=True)
-        if "num_categories" not in ckpt.get("feature_sampler_init_parameters", {}):
-            raise SystemExit(f"{model_config_path}: not an ABCD-VAE checkpoint (its feature sampler has no "
-                             "categories / codebook, e.g. the plain Gaussian VAE): decode.py decodes categories")
-        del ckpt
-        self.retrieve_model(checkpoint_path=model_config_path, device=device)
-        for m in (self.encoder, self.feature_sampler, self.decoder):
-            m.requires_grad_(False)
-            m.eval()
+    NOT_ABCD = ("not an ABCD-VAE checkpoint (its feature sampler has no categories / codebook, e.g. the plain "
+                "Gaussian VAE): decode.py decodes categories")
 
     def category_features(self, categories):
         """K' x D: the codebook's columns of the given categories."""
@@ -65,8 +55,8 @@ class Decoder(learning.Learner):
         """The result is written to a temporary path and takes save_path (an
         earlier output kept as .prev) only once the device status is clean, so
         a timed-out persistent launch or an error leaves nothing partial."""
-        tmp_path = save_path + ".partial.npz"
-        try:
+        with cli.replacing_outputs() as tmp:
+            tmp_path = tmp(save_path, ext=".npz")
             packed, lengths, (mu, lv), offl = self.decode(categories, **kw)
             arrays = dict(category_ix=np.asarray(categories, dtype=np.int64), lengths=lengths.cpu().numpy(),
                           batch_sizes=packed.batch_sizes.numpy(), sorted_indices=packed.sorted_indices.cpu().numpy(),
@@ -74,12 +64,6 @@ class Decoder(learning.Learner):
                           offset_logits=offl.cpu().numpy())
             np.savez(tmp_path, **arrays)
             _native.op_status.sync("decode")  # a timed-out persistent launch fails the run, not the file
-        except BaseException:
-            if os.path.isfile(tmp_path):
-                os.remove(tmp_path)
-            raise
-        rename_existing_file(save_path)
-        os.replace(tmp_path, save_path)
         return arrays
 
 
@@ -104,7 +88,7 @@ def get_parameters(argv=None):
                    help="a sequence ends at the first frame whose offset probability exceeds this")
     p.add_argument("--min_length", type=int, default=1, help="frames every sequence gets at least")
     p.add_argument("--speaker_ix", type=int, default=0, help="speaker index (models with a speaker embedding)")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
+    cli.add_device_argument(p)
     return p.parse_args(argv)
 
 

@@ -24,24 +24,17 @@ import numpy as np
 import pandas as pd
 import torch
 
+import cli
 import plain_learning
 from modules import _native, data_utils
-from modules.data_utils import Compose
 
 COLUMNS = ["data_ix", "parameter_name", "feature_dim", "parameter_value"]
 
 
-class Encoder(plain_learning.Learner):
+class Encoder(cli.FrozenCheckpoint, plain_learning.Learner):
     """A trained plain checkpoint (ours or the reference's, plain/learning.py
     keys) opened for inference: parameters frozen, modules in eval mode
     (plain/encode.py:12-20)."""
-
-    def __init__(self, model_config_path, device="cuda"):
-        self.device = torch.device(device)
-        self.retrieve_model(checkpoint_path=model_config_path, device=device)
-        for m in (self.encoder, self.feature_sampler, self.decoder):
-            m.requires_grad_(False)
-            m.eval()
 
     def _device_params(self, packed):
         with torch.no_grad():
@@ -99,22 +92,12 @@ def plain_annotation(annotation_file, sep=","):
 
 def get_parameters(argv=None):
     p = argparse.ArgumentParser(description="Encode annotated segments with a trained plain VAE (MI355X).")
-    p.add_argument("model_path", type=str, help="checkpoint.pt written by plain_learning.py or plain/learning.py")
-    p.add_argument("input_root", type=str, help="directory the annotation's wav paths are relative to")
-    p.add_argument("annotation_file", type=str, help="annotation table (csv) of the segments to encode")
-    p.add_argument("data_normalizer", type=float, help="log-amplitudes are divided by this (training's -N)")
-    p.add_argument("--annotation_sep", type=str, default=",", help="field separator of the annotation table")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
-    p.add_argument("-S", "--save_path", type=str, default=None,
-                   help="output csv (default: <input_root>/autoencoded.csv)")
-    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
-    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
-    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
-    p.add_argument("--fft_no_centering", action="store_true", help="STFT without centre padding")
-    p.add_argument("--channel", type=int, default=0, help="channel (0-based) of multi-channel wav files")
-    p.add_argument("-p", "--parameter_names", type=str, default=None, help="comma-separated parameter names")
-    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
-    p.add_argument("-b", "--batch_size", type=int, default=1, help="segments per forward pass")
+    cli.add_data_arguments(
+        p, table_help="annotation table (csv) of the segments to encode",
+        save_help="output csv (default: <input_root>/autoencoded.csv)",
+        model_help="checkpoint.pt written by plain_learning.py or plain/learning.py",
+        before_epsilon=lambda p: p.add_argument("-p", "--parameter_names", type=str, default=None,
+                                                help="comma-separated parameter names"))
     return p.parse_args(argv)
 
 
@@ -123,17 +106,10 @@ def main(argv=None):
     save_path = a.save_path or os.path.join(a.input_root, "autoencoded.csv")
     if os.path.dirname(save_path):
         os.makedirs(os.path.dirname(save_path), exist_ok=True)
-    parser = data_utils.Data_Parser(a.input_root, a.annotation_file, annotation_sep=a.annotation_sep)
-    fs = parser.get_sample_freq()
-    frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))
-    enc = Encoder(a.model_path, device=a.device)
-    eps, norm = a.epsilon, a.data_normalizer
-    tfm = Compose([data_utils.ToTensor(),
-                   data_utils.STFT(frame, hop, window=a.fft_window_type, centering=not a.fft_no_centering),
-                   data_utils.Transform(lambda x: (x + eps).log() / norm)])
+    dataset = cli.open_dataset(a)
     ix2name = {} if a.parameter_names is None else dict(enumerate(a.parameter_names.split(",")))
-    df = enc.encode_dataset(parser.get_data(transform=tfm, channel=a.channel), parameter_ix2name=ix2name,
-                            batch_size=a.batch_size)
+    df = Encoder(a.model_path, device=a.device).encode_dataset(dataset, parameter_ix2name=ix2name,
+                                                               batch_size=a.batch_size)
     df = df.sort_values(["data_ix", "parameter_name", "feature_dim"])
     ann = plain_annotation(a.annotation_file, a.annotation_sep)
     if "label" in ann.columns:

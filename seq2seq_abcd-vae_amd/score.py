@@ -31,31 +31,20 @@ import numpy as np
 import pandas as pd
 import torch
 
+import cli
 import learning
-from encode import rename_existing_file
 from modules import _native, data_utils, noise
-from modules.data_utils import Compose
 
 COLUMNS = ("data_ix", "length", "category_ix", "emission_nll", "end_prediction_loss", "kl_row", "kl_prior_share",
            "total")
 _TERMS = ("emission_nll", "end_prediction_loss", "kl_row", "kl_prior_share")
 
 
-class Scorer(learning.Learner):
+class Scorer(cli.FrozenCheckpoint, learning.Learner):
     """A trained ABCD checkpoint (ours or the reference's) opened for scoring:
     parameters frozen, modules in eval mode."""
-
-    def __init__(self, model_config_path, device="cuda"):
-        self.device = torch.device(device)
-        ckpt = torch.load(model_config_path, map_location="cpu", weights_only=True)
-        if "num_categories" not in ckpt.get("feature_sampler_init_parameters", {}):
-            raise SystemExit(f"{model_config_path}: not an ABCD-VAE checkpoint (its feature sampler has no "
-                             "categories, e.g. the plain Gaussian VAE): score.py scores the categorical model")
-        del ckpt
-        self.retrieve_model(checkpoint_path=model_config_path, device=device)
-        for m in (self.encoder, self.feature_sampler, self.decoder):
-            m.requires_grad_(False)
-            m.eval()
+    NOT_ABCD = ("not an ABCD-VAE checkpoint (its feature sampler has no categories, e.g. the plain Gaussian VAE): "
+                "score.py scores the categorical model")
 
     def score_batch(self, packed, is_offset, speaker, num_strings, sample=False, samples=1):
         """One batch -> {column: B device values in the batch's packed row order}
@@ -106,23 +95,14 @@ def score_table(score_batch, dataset, save_path, batch_size=1, finish=None, colu
     ``score_batch(...)["long"]``, a dict holding ``row`` (the packed row each
     long row belongs to, mapped to ``data_ix`` here) and the ``long_columns``
     (``(name, dtype)``), in the order the rows are to be written."""
-    paths = [(save_path, save_path + ".partial")]
-    if long_path is not None:
-        paths.append((long_path, long_path + ".partial"))
-    ann = None
-    if "label" in dataset.df_annotation.columns:
-        ann = dataset.df_annotation.drop(columns=["onset_ix", "offset_ix", "length"])
+    ann = cli.annotation_columns(dataset)
 
     def host(v):
         return v.cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
 
-    def with_annotation(table):
-        if ann is None:
-            return table
-        return pd.concat([table, ann.reindex(table["data_ix"].to_numpy()).reset_index(drop=True)], axis=1)
-
     header, written = True, 0
-    try:
+    with cli.replacing_outputs() as tmp:
+        tmp_path, long_tmp_path = tmp(save_path), long_path and tmp(long_path)
         for packed, is_offset, speaker, ixs in data_utils.DataLoader(dataset, batch_size=batch_size, shuffle=False):
             out = score_batch(packed, is_offset, speaker)
             ix = np.asarray(ixs, dtype=np.int64)
@@ -135,47 +115,25 @@ def score_table(score_batch, dataset, save_path, batch_size=1, finish=None, colu
             if len(table) != len(ix):
                 raise RuntimeError(f"score_batch returned {len(table)} rows for a batch of {len(ix)} segments")
             mode = "w" if header else "a"
-            with_annotation(table).to_csv(paths[0][1], index=False, mode=mode, header=header)
+            cli.join_annotation(table, ann).to_csv(tmp_path, index=False, mode=mode, header=header)
             if long_path is not None:
                 long = out["long"]
                 lt = pd.DataFrame({"data_ix": ix[host(long["row"]).astype(np.int64)]})
                 for name, kind in long_columns:
                     lt[name] = host(long[name]).astype(kind)
-                with_annotation(lt).to_csv(paths[1][1], index=False, mode=mode, header=header)
+                cli.join_annotation(lt, ann).to_csv(long_tmp_path, index=False, mode=mode, header=header)
             header = False
             written += len(table)
         if finish is not None:
             finish()  # a timed-out persistent launch fails the run, not the table
-    except BaseException:
-        for _, tmp_path in paths:
-            if os.path.isfile(tmp_path):
-                os.remove(tmp_path)
-        raise
-    for path, tmp_path in paths:
-        if os.path.isfile(tmp_path):  # (an empty dataset writes no table, as encode.py)
-            rename_existing_file(path)
-            os.replace(tmp_path, path)
     return written
 
 
 def get_parameters(argv=None):
     p = argparse.ArgumentParser(description="Score annotated segments under a trained ABCD-VAE (MI355X): "
                                             "per-segment emission NLL, end-prediction loss and KL.")
-    p.add_argument("model_path", type=str, help="checkpoint.pt written by learning.py (this package or the reference)")
-    p.add_argument("input_root", type=str, help="directory the annotation's wav paths are relative to")
-    p.add_argument("annotation_file", type=str, help="annotation table (csv) of the segments to score")
-    p.add_argument("data_normalizer", type=float, help="log-amplitudes are divided by this (training's -N)")
-    p.add_argument("--annotation_sep", type=str, default=",", help="field separator of the annotation table")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
-    p.add_argument("-S", "--save_path", type=str, default=None,
-                   help="output csv (default: <input_root>/scores.csv); an existing file is kept as .prev")
-    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
-    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
-    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
-    p.add_argument("--fft_no_centering", action="store_true", help="STFT without centre padding")
-    p.add_argument("--channel", type=int, default=0, help="channel (0-based) of multi-channel wav files")
-    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
-    p.add_argument("-b", "--batch_size", type=int, default=1, help="segments per forward pass")
+    cli.add_data_arguments(p, table_help="annotation table (csv) of the segments to score",
+                           save_help="output csv (default: <input_root>/scores.csv); an existing file is kept as .prev")
     how = p.add_mutually_exclusive_group()
     how.add_argument("--mean", action="store_true",
                      help="deterministic score (default): softmax features, the emission mean fed back")
@@ -199,18 +157,11 @@ def main(argv=None):
     save_path = a.save_path or os.path.join(a.input_root, "scores.csv")
     if os.path.dirname(save_path):
         os.makedirs(os.path.dirname(save_path), exist_ok=True)
-    parser = data_utils.Data_Parser(a.input_root, a.annotation_file, annotation_sep=a.annotation_sep)
-    fs = parser.get_sample_freq()
-    frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))
+    dataset = cli.open_dataset(a)
     scorer = Scorer(a.model_path, device=a.device)
     if a.seed is not None:
         noise.manual_seed(a.seed)
-    eps, norm = a.epsilon, a.data_normalizer
-    tfm = Compose([data_utils.ToTensor(),
-                   data_utils.STFT(frame, hop, window=a.fft_window_type, centering=not a.fft_no_centering),
-                   data_utils.Transform(lambda x: (x + eps).log() / norm)])
-    scorer.score_dataset(parser.get_data(transform=tfm, channel=a.channel), save_path, batch_size=a.batch_size,
-                         sample=a.sample, samples=a.samples)
+    scorer.score_dataset(dataset, save_path, batch_size=a.batch_size, sample=a.sample, samples=a.samples)
     return save_path
 
 

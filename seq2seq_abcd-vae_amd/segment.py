@@ -40,8 +40,8 @@ import scipy.io.wavfile as spw
 import torch
 
 import classify
-from encode import rename_existing_file
-from modules import _native, data_utils, segmentation
+import cli
+from modules import _native, segmentation
 
 COLUMNS = ("onset", "offset", "input_path", "data_type", "speaker", "label", "category_ix", "length", "segment_score")
 
@@ -104,15 +104,8 @@ def write_segments(save_path, rows):
     """Writes the annotation table (an existing file is kept as .prev, nothing
     partial is left behind).  Returns the number of rows."""
     df = pd.DataFrame(rows, columns=list(COLUMNS))
-    tmp = save_path + ".partial"
-    try:
-        df.to_csv(tmp, index=False)
-    except BaseException:
-        if os.path.isfile(tmp):
-            os.remove(tmp)
-        raise
-    rename_existing_file(save_path)
-    os.replace(tmp, save_path)
+    with cli.replacing_outputs() as tmp:
+        df.to_csv(tmp(save_path), index=False)
     return len(df)
 
 
@@ -141,28 +134,18 @@ def get_parameters(argv=None):
     import argparse
     p = argparse.ArgumentParser(description="Cut recordings into labelled segments with a trained ABCD-VAE's decoder "
                                             "(MI355X): span scores under every category and a semi-Markov cover.")
-    p.add_argument("model_path", type=str, help="checkpoint.pt written by learning.py (this package or the reference)")
-    p.add_argument("input_root", type=str, help="directory the table's wav paths are relative to")
-    p.add_argument("recording_table", type=str,
-                   help="table (csv) with an input_path column; an existing annotation works (its distinct paths)")
-    p.add_argument("data_normalizer", type=float, help="log-amplitudes are divided by this (training's -N)")
-    p.add_argument("--annotation_sep", type=str, default=",", help="field separator of the tables")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
-    p.add_argument("-S", "--save_path", type=str, default=None,
-                   help="output csv (default: <input_root>/segmented.csv); an existing file is kept as .prev")
-    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
-    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
-    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
-    p.add_argument("--fft_no_centering", action="store_true", help="STFT without centre padding")
-    p.add_argument("--channel", type=int, default=0, help="channel (0-based) of multi-channel wav files")
-    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
+    cli.add_data_arguments(
+        p, table="recording_table",
+        table_help="table (csv) with an input_path column; an existing annotation works (its distinct paths)",
+        save_help="output csv (default: <input_root>/segmented.csv); an existing file is kept as .prev",
+        root_help="directory the table's wav paths are relative to", sep_help="field separator of the tables",
+        batch=False)
     p.add_argument("--max_length", type=int, required=True, help="longest segment, frames")
     p.add_argument("--min_length", type=int, default=1,
                    help="shortest segment, frames (raised to the shortest the loader can featurise again)")
-    p.add_argument("--prior", type=str, default="dirichlet", choices=classify.PRIORS,
-                   help="log weights of the categories: the Dirichlet posterior's E[log pi_k] (default) or zero")
-    p.add_argument("--entire_data_size", type=float, default=None,
-                   help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the table's rows)")
+    cli.add_prior_arguments(
+        p, prior_help="log weights of the categories: the Dirichlet posterior's E[log pi_k] (default) or zero",
+        size_help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the table's rows)")
     p.add_argument("--segment_bonus", type=float, default=0.0,
                    help="log prior added per segment; negative values discourage over-segmentation")
     p.add_argument("--gap_score", type=float, default=None,
@@ -181,8 +164,7 @@ def get_parameters(argv=None):
         p.error("--max_length must lie in 1 .. 16383")
     if a.min_length < 1 or a.min_length > a.max_length:
         p.error("--min_length must lie in 1 .. --max_length")
-    if a.entire_data_size is not None and not a.entire_data_size > 0:
-        p.error("--entire_data_size must be positive")
+    cli.check_prior_arguments(p, a)
     if sum(v is not None for v in (a.gap_score, a.gap_model, a.fit_gap)) > 1:
         p.error("--gap_score, --gap_model and --fit_gap exclude one another")
     if (a.fit_gap is None) != (a.gap_model_out is None):
@@ -204,16 +186,14 @@ def main(argv=None):
     if seg.decoder.embed_speaker is not None and a.speaker is None:
         raise SystemExit("this checkpoint's decoder embeds speakers: --speaker is required")
     centering = not a.fft_no_centering
-    eps, norm = a.epsilon, a.data_normalizer
-    stft = {}
+    spectrum = {}
 
     def featurise(path):
         fs, wave = read_wave(a.input_root, path, a.channel)
-        frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))
-        if (frame, hop) not in stft:
-            stft[frame, hop] = data_utils.STFT(frame, hop, window=a.fft_window_type, centering=centering)
-        frames = (stft[frame, hop](torch.from_numpy(wave)) + eps).log() / norm
-        return fs, frame, hop, len(wave), frames.to(seg.device)
+        frame, hop = cli.frame_hop(a, fs)
+        if (frame, hop) not in spectrum:
+            spectrum[frame, hop] = cli.log_spectrum(a, frame, hop)
+        return fs, frame, hop, len(wave), spectrum[frame, hop](torch.from_numpy(wave)).to(seg.device)
 
     gap_model = None
     if a.fit_gap is not None:

@@ -36,9 +36,8 @@ import pandas as pd
 import torch
 
 import classify
-from encode import rename_existing_file
+import cli
 from modules import _native, data_utils, ops
-from modules.data_utils import Compose
 from modules.sequence import TransitionModel, split_sequences
 
 COLUMNS = ("data_ix", "sequence_ix", "position", "decoder_category_ix", "smoothed_category_ix",
@@ -118,9 +117,7 @@ def run(seqr, dataset, save_dir, batch_size=1, prior="dirichlet", entire_data_si
                         "decoder_category_ix": best, "smoothed_category_ix": smooth.cpu().numpy(),
                         "smoothed_category_prob": prob.double().cpu().numpy(), "viterbi_category_ix": vit,
                         "changed": (vit != best).astype(np.int64)})
-    if "label" in ann.columns:
-        keep = ann.drop(columns=[c for c in ("onset_ix", "offset_ix", "length") if c in ann.columns])
-        seg = pd.concat([seg, keep.reindex(order).reset_index(drop=True)], axis=1)
+    seg = cli.join_annotation(seg, cli.annotation_columns(dataset))
     ft, tt = np.divmod(np.arange(K * K), K)
     tr = pd.DataFrame({"from_ix": ft, "to_ix": tt,
                        "probability": model.log_trans.double().exp().reshape(-1).cpu().numpy(),
@@ -129,11 +126,9 @@ def run(seqr, dataset, save_dir, batch_size=1, prior="dirichlet", entire_data_si
                        "context_free_log_evidence": cf.cpu().numpy()})
     _native.op_status.sync("sequence.py")
     tables = dict(zip(FILES, (seg, tr, sq)))
-    for name, table in tables.items():  # every table is complete before any earlier one is moved aside
-        table.to_csv(os.path.join(save_dir, name + ".partial"), index=False)
-    for name in tables:
-        rename_existing_file(os.path.join(save_dir, name))
-        os.replace(os.path.join(save_dir, name + ".partial"), os.path.join(save_dir, name))
+    with cli.replacing_outputs() as tmp:  # every table is complete before any earlier one is moved aside
+        for name, table in tables.items():
+            table.to_csv(tmp(os.path.join(save_dir, name)), index=False)
     return tables
 
 
@@ -141,26 +136,12 @@ def get_parameters(argv=None):
     import argparse
     p = argparse.ArgumentParser(description="Label annotated segments in context (MI355X): a hidden Markov model over "
                                             "the category sequence of every recording, fitted by EM.")
-    p.add_argument("model_path", type=str, help="checkpoint.pt written by learning.py (this package or the reference)")
-    p.add_argument("input_root", type=str, help="directory the annotation's wav paths are relative to")
-    p.add_argument("annotation_file", type=str, help="annotation table (csv) of the segments to label")
-    p.add_argument("data_normalizer", type=float, help="log-amplitudes are divided by this (training's -N)")
-    p.add_argument("--annotation_sep", type=str, default=",", help="field separator of the annotation table")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
-    p.add_argument("-S", "--save_path", type=str, default=None,
-                   help="output directory (default: <input_root>); existing tables are kept as .prev")
-    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
-    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
-    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
-    p.add_argument("--fft_no_centering", action="store_true", help="STFT without centre padding")
-    p.add_argument("--channel", type=int, default=0, help="channel (0-based) of multi-channel wav files")
-    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
-    p.add_argument("-b", "--batch_size", type=int, default=1, help="segments per forward pass")
-    p.add_argument("--prior", type=str, default="dirichlet", choices=classify.PRIORS,
-                   help="the initial, context-free model: every row softmax of the Dirichlet posterior's E[log pi_k] "
-                        "(default) or uniform")
-    p.add_argument("--entire_data_size", type=float, default=None,
-                   help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the number of segments)")
+    cli.add_data_arguments(p, table_help="annotation table (csv) of the segments to label",
+                           save_help="output directory (default: <input_root>); existing tables are kept as .prev")
+    cli.add_prior_arguments(
+        p, prior_help="the initial, context-free model: every row softmax of the Dirichlet posterior's E[log pi_k] "
+                      "(default) or uniform",
+        size_help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the number of segments)")
     p.add_argument("--em_iterations", type=int, default=10, help="EM iterations of the transition matrix (0: none)")
     p.add_argument("--pseudo_count", type=float, default=None,
                    help="added to every expected count in the M-step (default: 1 / K)")
@@ -171,8 +152,7 @@ def get_parameters(argv=None):
     p.add_argument("--transitions", type=str, default=None,
                    help="a transitions.csv to load instead of fitting one")
     a = p.parse_args(argv)
-    if a.entire_data_size is not None and not a.entire_data_size > 0:
-        p.error("--entire_data_size must be positive")
+    cli.check_prior_arguments(p, a)
     if a.em_iterations < 0:
         p.error("--em_iterations must not be negative")
     if a.pseudo_count is not None and not a.pseudo_count >= 0:
@@ -186,15 +166,8 @@ def main(argv=None):
     a = get_parameters(argv)
     save_dir = a.save_path or a.input_root
     os.makedirs(save_dir, exist_ok=True)
-    parser = data_utils.Data_Parser(a.input_root, a.annotation_file, annotation_sep=a.annotation_sep)
-    fs = parser.get_sample_freq()
-    frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))
-    seqr = Sequencer(a.model_path, device=a.device)
-    eps, norm = a.epsilon, a.data_normalizer
-    tfm = Compose([data_utils.ToTensor(),
-                   data_utils.STFT(frame, hop, window=a.fft_window_type, centering=not a.fft_no_centering),
-                   data_utils.Transform(lambda x: (x + eps).log() / norm)])
-    run(seqr, parser.get_data(transform=tfm, channel=a.channel), save_dir, batch_size=a.batch_size, prior=a.prior,
+    dataset = cli.open_dataset(a)
+    run(Sequencer(a.model_path, device=a.device), dataset, save_dir, batch_size=a.batch_size, prior=a.prior,
         entire_data_size=a.entire_data_size, em_iterations=a.em_iterations, pseudo_count=a.pseudo_count,
         max_gap=a.max_gap, sequence_columns=tuple(a.sequence_columns), transitions=a.transitions)
     return save_dir

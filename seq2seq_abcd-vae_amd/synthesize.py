@@ -24,7 +24,7 @@ import pandas as pd
 import scipy.io.wavfile as spw
 import torch
 
-from encode import rename_existing_file
+import cli
 from modules import _native, data_utils
 
 COLUMNS = ("index", "category_ix", "frames", "samples", "residual", "clipped_samples", "path")
@@ -53,8 +53,7 @@ def synthesize_to_dir(arrays, save_dir, fs, vocoder, field="mu", n_iter=32, mome
                          f"frame) gives {F}: pass the sampling rate and --fft_frame_length of the model's training data")
     cats = np.asarray(arrays["category_ix"], dtype=np.int64) if "category_ix" in arrays else None
     os.makedirs(save_dir, exist_ok=True)
-    written = []  # (temporary, final)
-    try:
+    with cli.replacing_outputs() as tmp:
         waves, n_samples, residual = vocoder((data, bs), n_iter=n_iter, momentum=momentum, seed=seed)
         waves, residual = waves.cpu().numpy(), residual.cpu().numpy()
         rows = []
@@ -68,24 +67,12 @@ def synthesize_to_dir(arrays, save_dir, fs, vocoder, field="mu", n_iter=32, mome
                     out = waves[j, :n].astype(np.float32)
                 else:
                     out, row["clipped_samples"] = to_int16(waves[j, :n])
-                tmp = os.path.join(save_dir, name + ".partial")
-                spw.write(tmp, int(fs), out)
-                written.append((tmp, os.path.join(save_dir, name)))
+                spw.write(tmp(os.path.join(save_dir, name)), int(fs), out)
                 row["path"] = name
             rows.append(row)
         table = pd.DataFrame(sorted(rows, key=lambda r: r["index"]), columns=list(COLUMNS))
-        tmp = os.path.join(save_dir, "synthesis.csv.partial")
-        table.to_csv(tmp, index=False)
-        written.append((tmp, os.path.join(save_dir, "synthesis.csv")))
+        table.to_csv(tmp(os.path.join(save_dir, "synthesis.csv")), index=False)
         _native.op_status.sync("synthesize")
-    except BaseException:
-        for tmp, _ in written:
-            if os.path.isfile(tmp):
-                os.remove(tmp)
-        raise
-    for tmp, final in written:
-        rename_existing_file(final)
-        os.replace(tmp, final)
     return table
 
 
@@ -96,16 +83,12 @@ def get_parameters(argv=None):
     p.add_argument("data_normalizer", type=float, help="the normaliser N of log(|STFT| + eps) / N used in training")
     p.add_argument("-S", "--save_dir", type=str, required=True, help="output directory")
     p.add_argument("--field", type=str, default="mu", help="which frames to invert: mu (default) or data")
-    p.add_argument("--fft_frame_length", type=float, default=0.008, help="STFT window length, seconds")
-    p.add_argument("--fft_step_size", type=float, default=0.004, help="STFT hop, seconds")
-    p.add_argument("--fft_window_type", type=str, default="hann_window", help="torch window function name")
-    p.add_argument("--fft_no_centering", action="store_true", help="not supported: see the message")
-    p.add_argument("-E", "--epsilon", type=float, default=2 ** (-15), help="offset inside log(|STFT| + eps)")
+    cli.add_stft_arguments(p, no_centering_help="not supported: see the message", channel=False)
     p.add_argument("--iterations", type=int, default=32, help="Griffin-Lim iterations")
     p.add_argument("--momentum", type=float, default=0.99, help="0: classic Griffin-Lim; 0.99: the fast variant")
     p.add_argument("--seed", type=int, default=0, help="seed of the random initial phase")
     p.add_argument("--float32", action="store_true", help="write float32 wavs instead of saturated int16")
-    p.add_argument("-d", "--device", type=str, default="cuda", help="GPU device (there is no CPU path)")
+    cli.add_device_argument(p)
     return p.parse_args(argv)
 
 
@@ -115,7 +98,7 @@ def main(argv=None):
         raise SystemExit("synthesize.py: an STFT without centre padding cannot be inverted at the edges (a Hann window "
                          "violates the overlap-add condition there; the library returns ABCD_EINVAL for center = 0)")
     fs = a.sampling_rate
-    frame, hop = int(np.floor(a.fft_frame_length * fs)), int(np.floor(a.fft_step_size * fs))  # as encode.py
+    frame, hop = cli.frame_hop(a, fs)
     voc = data_utils.DeviceVocoder(frame, hop, window=a.fft_window_type, eps=a.epsilon, normalizer=a.data_normalizer,
                                    device=a.device)
     with np.load(a.decoded_path, allow_pickle=False) as z:
