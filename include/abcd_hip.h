@@ -782,8 +782,25 @@ void abcd_dispatch_reset(void);
  * abcd_debug_xcc_map -- launches `blocks` one-per-CU workgroups that record
  * their (XCC id, HW_ID) pair into dev_out[2 * block], dev_out[2 * block + 1]
  * (dev_out holds 2 * blocks u32; the placement the persistent kernels' group
- * roles rely on).  Returns 0 / a HIP error. */
+ * roles rely on).  Returns 0 / a HIP error;
+ * abcd_debug_gemm_route -- names what the calling thread's last GEMM
+ * dispatch (abcd_gemm_nt / abcd_gemm_tn / abcd_linear / the products of
+ * abcd_linear_backward, and every GEMM inside the other entry points)
+ * launched: "x6r8<5,128>", "x6r8<5,128,t16>", "x6r8<8,64>", "x6f", "x6t",
+ * "x6s<4,5>", "x6s<4,4,kc>", "x6s<5,4,one>", "tn<4,8,kc>", "ks", "big"; where
+ * split-K ran, " z=<Z> <reduce>" follows with the slab reduction's form
+ * (zg4, zg16, vec, scalar), and the un-split gemm_ks reads "ks z=1".  "" before
+ * the first dispatch.  The string is thread-local and valid until the
+ * thread's next dispatch; each launch stores the name's pointer (and the
+ * slab count) on the host, no device work;
+ * abcd_debug_gemm_side -- sets (on != 0) or clears the calling thread's
+ * side-stream GEMM mode, the one the training step enters beside a
+ * persistent recurrent kernel: abcd_gemm_nt / abcd_gemm_tn then take the
+ * small-footprint routes.  For tests; nothing in the training path calls
+ * either. */
 void abcd_debug_persist_prof(unsigned long long* dev_buf, int mask);
+const char* abcd_debug_gemm_route(void);
+void abcd_debug_gemm_side(int on);
 /* Side-stream gate (per calling host thread, default off): read by a deferred
  * abcd_decoder_backward_dropout(..., ABCD_DEFER_PARAMS).  The first encoder
  * BPTT this thread launches persistently after it becomes the gate's target,

@@ -31,6 +31,15 @@ static thread_local int tl_side = 0;
 GemmSideScope::GemmSideScope(bool on) : prev(tl_side) { tl_side = on ? 1 : prev; }  // off: keep the caller's mode
 GemmSideScope::~GemmSideScope() { tl_side = prev; }
 
+// abcd_debug_gemm_route: what this thread's last dispatch launched.  Every
+// *_launch stores its name (a host pointer store, no device work); gemm_ks and
+// slab_reduce add the slab count and the reduction's form.
+static thread_local const char* tl_route = "";
+static thread_local const char* tl_route_red = "";
+static thread_local int tl_route_z = 0;  // 0: no " z=" suffix
+static inline void route_set(const char* name) { tl_route = name, tl_route_red = "", tl_route_z = 0; }
+static inline void route_split(int Z, const char* red) { tl_route_z = Z, tl_route_red = red; }
+
 int stream_fork(hipStream_t from, hipStream_t to, int slot) {
   if (from == to) return 0;
   static std::mutex mu;
@@ -199,13 +208,16 @@ static int slab_reduce(hipStream_t s, const float* slab, int Z, const EpiArgs& e
   if (n % 4 == 0 && ((uintptr_t)slab & 15) == 0 && Z >= 4) {
     // the fewest thread groups per quad that give >= 512 workgroups (2 per CU)
     if (nq >= 512 * 64 || Z < 16) {
+      route_split(Z, "zg4");
       slab_reduce_zg_kernel<4><<<(int)cdiv(nq, 64), 256, 0, s>>>(slab, Z, e);
     } else {
+      route_split(Z, "zg16");
       slab_reduce_zg_kernel<16><<<(int)cdiv(nq, 16), 256, 0, s>>>(slab, Z, e);
     }
     ABCD_CHECK_LAUNCH();
     return 0;
   }
+  route_split(Z, n % 4 == 0 && ((uintptr_t)slab & 15) == 0 ? "vec" : "scalar");  // slab_reduce_kernel's own test
   slab_reduce_kernel<<<(int)std::max<long>(1, std::min<long>(2048, cdiv(n / 4 + 1, 256))), 256, 0, s>>>(slab, Z, e);
   ABCD_CHECK_LAUNCH();
   return 0;
@@ -218,6 +230,7 @@ static int gemm_launch(hipStream_t s, int M, int N, int K, OA A, OB B, EpiArgs e
   const int tiles_big = cdiv(M, 128) * cdiv(N, 128);
   if (tiles_big >= 240) {
     dim3 grid(cdiv(N, 128), cdiv(M, 128), 1);
+    route_set("big");
     gemm_big_kernel<4, 4, OA, OB><<<grid, 256, 0, s>>>(A, B, nch, nch, e);
     ABCD_CHECK_LAUNCH();
     return 0;
@@ -236,6 +249,8 @@ static int gemm_launch(hipStream_t s, int M, int N, int K, OA A, OB B, EpiArgs e
   dim3 grid(cdiv(N, 64), cdiv(M, 32), Z);
   EpiArgs ek = e;
   if (Z > 1) ek.slab = scratch;
+  route_set("ks");
+  route_split(Z, "");
   gemm_ks_kernel<2, 4, OA, OB><<<grid, 256, 0, s>>>(A, B, nch, cps, ek);
   ABCD_CHECK_LAUNCH();
   if (Z > 1) {
@@ -486,6 +501,8 @@ static int gemm_tn_launch(hipStream_t s, int M, int N, int K, const float* A, lo
   Z = cdiv(K, kps);
   EpiArgs ek = e;
   if (Z > 1) ek.slab = scratch;
+  route_set(MR == 4 && NR == 8 ? (AKC && BKC ? "tn<4,8,kc>" : "tn<4,8>")
+                               : MR == 4 && NR == 4 ? (AKC && BKC ? "tn<4,4,kc>" : "tn<4,4>") : "tn");
   gemm_tn_kernel<MR, NR, AKC, BKC><<<dim3(cdiv(N, BN), cdiv(M, BM), Z), 256, 0, s>>>(A, lda, B, ldb, K, kps, ek,
                                                                                    1);
   ABCD_CHECK_LAUNCH();
@@ -818,6 +835,7 @@ static int gemm_x6f_launch(hipStream_t s, int M, int N, int K, const float* A, l
                            EpiArgs e) {
   constexpr int BM = 32 * MR, BN = 32 * NR;
   const size_t lds = (size_t)(BM / 16 + BN / 16) * 3 * 64 * 16;
+  route_set("x6f");
   gemm_x6f_kernel<MR, NR><<<dim3(cdiv(N, BN), cdiv(M, BM), 1), 256, lds, s>>>(A, lda, B, ldb, K, e, 1);
   ABCD_CHECK_LAUNCH();
   return 0;
@@ -935,6 +953,8 @@ __global__ __launch_bounds__(512, 1) void gemm_x6r8_kernel(const float* __restri
   };
   constexpr int RB = 16 * MR;
   const int ec = n0 + 4 * (lane % (BN / 4));
+  // 16-B row stores only where every row of C starts 16-B aligned (as gemm_tn_tile's `vec`)
+  const bool cvec = (e.ldc % 4 == 0) && (((uintptr_t)e.C & 15) == 0);
   f4 bq = f4zero(), w2q = f4zero();
   if (e.bias) {
 #pragma unroll
@@ -1059,7 +1079,7 @@ __global__ __launch_bounds__(512, 1) void gemm_x6r8_kernel(const float* __restri
               for (int t = 0; t < 4; ++t) val[t] = tanhf(val[t]);
             }
             if constexpr (MODE == 1) pl = val[0] * w2q[0] + val[1] * w2q[1] + val[2] * w2q[2] + val[3] * w2q[3];
-            if (col + 4 <= N) *reinterpret_cast<f4*>(d) = val;
+            if (cvec && col + 4 <= N) *reinterpret_cast<f4*>(d) = val;
             else
 #pragma unroll
               for (int t = 0; t < 4; ++t)
@@ -1104,6 +1124,8 @@ static int gemm_x6r8_launch(hipStream_t s, int M, int N, int K, const float* A, 
                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     attr = true;
   }
+  route_set(MODE == 1 ? "x6r8<8,64,offset_fwd>" : MODE == 2 ? "x6r8<8,64,offset_bwd>"
+            : NC == 8 ? "x6r8<8,64>" : T16 ? "x6r8<5,128,t16>" : "x6r8<5,128>");
   gemm_x6r8_kernel<NC, BN, MR, HR, MODE, T16><<<gr.grid, 512, lds, s>>>(A, lda, B, ldb, K, e, gr.nslices, gr.rows_per, oa);
   ABCD_CHECK_LAUNCH();
   return 0;
@@ -1319,6 +1341,7 @@ static int gemm_x6t_launch(hipStream_t s, int M, int N, int K, const float* A, l
   EpiArgs ek = e;
   if (Z > 1) ek.slab = scratch;
   const size_t lds = (size_t)(BM / 16 + BN / 16) * (3 * 64 + 1) * 16;
+  route_set("x6t");
   gemm_x6t_kernel<MR, NR><<<dim3(cdiv(N, BN), cdiv(M, BM), Z), 256, lds, s>>>(A, lda, B, ldb, K, kps, ek, 1);
   ABCD_CHECK_LAUNCH();
   if (Z > 1) {
@@ -1871,6 +1894,8 @@ static int gemm_x6s_launch(hipStream_t s, int M, int N, int K, const float* A, l
   Z = cdiv(K, kps);
   EpiArgs ek = e;
   if (Z > 1) ek.slab = scratch;
+  route_set(AKC ? "x6s<4,4,kc>" : MR == 5 ? "x6s<5,4,one>"
+            : NR == 5 ? (ONE ? "x6s<4,5,one>" : "x6s<4,5>") : (ONE ? "x6s<4,4,one>" : "x6s<4,4>"));
   gemm_x6s_kernel<MR, NR, AKC, BKC, ONE><<<dim3(cdiv(N, BN), cdiv(M, BM), Z), 256, 0, s>>>(A, lda, B, ldb, K, kps,
                                                                                           ek, 1);
   ABCD_CHECK_LAUNCH();
@@ -2426,6 +2451,16 @@ extern "C" int abcd_linear_backward(int M, int N, int K, const float* x, long ld
   if (db) ABCD_TRY((hipError_t)colsum(s, dyp, Np, M, N, nullptr, db, 0.f, sc, (size_t)1 << 20));
   return 0;
 }
+
+// diagnostics (abcd_hip.h)
+extern "C" const char* abcd_debug_gemm_route(void) {
+  using namespace abcd;
+  static thread_local char buf[64];
+  if (tl_route_z <= 0) return tl_route;
+  snprintf(buf, sizeof buf, "%s z=%d%s%s", tl_route, tl_route_z, tl_route_red[0] ? " " : "", tl_route_red);
+  return buf;
+}
+extern "C" void abcd_debug_gemm_side(int on) { abcd::tl_side = on ? 1 : 0; }
 
 extern "C" int abcd_fill_dropout(float* out, long n, float p, uint64_t seed, uint64_t offset, void* stream) {
   if (!out || n < 0 || !(p >= 0.f && p < 1.f)) return ABCD_EINVAL;

@@ -202,6 +202,8 @@ _SIGS = {
     "abcd_dispatch_count": (c_long, [c_int]),
     "abcd_dispatch_reset": (None, []),
     "abcd_debug_persist_prof": (None, [c_void_p, c_int]),
+    "abcd_debug_gemm_route": (ctypes.c_char_p, []),
+    "abcd_debug_gemm_side": (None, [c_int]),
     "abcd_side_gate_enable": (None, [c_int]),
     "abcd_debug_xcc_map": (c_int, [c_void_p, c_int, c_void_p]),
     "abcd_fill_normal": (c_int, [c_void_p, c_long, c_uint64, c_uint64, c_void_p]),

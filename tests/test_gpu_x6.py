@@ -18,6 +18,9 @@ def _err(c, ref):
     return float((c.double() - ref).abs().max() / ref.abs().max())
 
 
+FRAME_ROUTE = {144: "x6r8<5,128,t16>", 256: "x6r8<8,64>", 400: "x6f"}   # by K: what abcd_debug_gemm_route names
+
+
 @pytest.mark.parametrize("M,N,K", [(32768, 1024, 144), (32768, 512, 256), (16384, 1024, 400)])
 def test_x6_frame_gemm_fp32_accurate(M, N, K):
     from modules import _native as Nn
@@ -28,6 +31,7 @@ def test_x6_frame_gemm_fp32_accurate(M, N, K):
     ws = Nn.workspace(64 << 20, "cuda")
     Nn.check(Nn.lib().abcd_gemm_nt(M, N, K, Nn.ptr(A), K, Nn.ptr(B), K, Nn.ptr(C), N, None, Nn.ptr(ws), ws.numel(),
                                    Nn.stream()), "gemm_nt")
+    assert Nn.lib().abcd_debug_gemm_route().decode() == FRAME_ROUTE[K]
     ref = A.double() @ B.double().t()
     e32 = _err(A @ B.t(), ref)
     e6 = _err(C, ref)
@@ -45,6 +49,8 @@ def test_x6_weight_gradient_gemm_fp32_accurate(M, N, K, ldb):
     ws = Nn.workspace(256 << 20, "cuda")
     Nn.check(Nn.lib().abcd_gemm_tn(M, N, K, Nn.ptr(A), M, Nn.ptr(Bf), ldb, Nn.ptr(C), N, Nn.ptr(ws), ws.numel(),
                                    Nn.stream()), "gemm_tn")
+    route = Nn.lib().abcd_debug_gemm_route().decode().split(" ")[0]   # " z=<Z> <reduce>" follows
+    assert route == ("x6s<4,5>" if N == 129 else "x6t"), route
     B = Bf[:, :N]
     ref = A.double().t() @ B.double()
     e32 = _err(A.t() @ B, ref)
