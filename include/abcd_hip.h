@@ -625,6 +625,74 @@ int abcd_span_viterbi(const double* span_score, const int32_t* span_cat, long ld
                       void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Time-warped scoring: a segment aligned to a prototype.  abcd_pairwise_nll
+ * scores frame t against step t; here the T_proto steps of prototype p are the
+ * states of a left-to-right HMM and frame t of segment b is emitted by state
+ * a(t), with a(0) = 0 and a(t + 1) - a(t) = m in {0, 1, 2} (stay, step, skip)
+ * at a cost of -log_move[m].  x, gt_offset and the prototype rectangle are
+ * those of abcd_pairwise_nll, except that T_proto (1 .. 16383) may be shorter
+ * or longer than x->T.  log_move is a HOST array of three doubles; -inf
+ * disables a move.  band < 0: no band; otherwise cells with |s - t| > band do
+ * not exist.  With r = off_t + b,
+ *   e(t,s) = 0.5 sum_f (log 2pi + lv[s,p,f] + (x[r,f] - mu[s,p,f])^2 e^-lv[s,p,f])
+ *            (fp32, one frame's F columns exactly as abcd_pairwise_nll sums them),
+ *   o(t,s) = max(v,0) - v y[r] + log1p(e^-|v|),  v = proto_offset_logits[s P + p]  (fp32),
+ *   c(t,s) = e(t,s) + o(t,s), and in fp64
+ *   D[0,0] = c(0,0), D[0,s>0] = +inf,
+ *   D[t,s] = c(t,s) + (+)_{m, s-m >= 0} (D[t-1,s-m] - log_move[m]),
+ *   warp[b ld_warp + p] = (+)_s D[len_b - 1, s],
+ * where (+) is min (marginal = 0: the best alignment) or -log sum exp(-.)
+ * (marginal != 0: all alignments).  A disabled move, a +inf predecessor, a
+ * cell outside the band and a NaN cost are excluded; a cell with nothing left
+ * is +inf, and a pair no alignment reaches gets warp = +inf (which
+ * abcd_pair_posterior excludes).  Viterbi ties go to the lowest move, then to
+ * the lowest final state.  With log_move = (-inf, 0, -inf) and T_proto >= len_b
+ * warp is pair_em + pair_off up to the order of the fp64 sums.
+ *
+ * abcd_warp_nll: one workgroup per (b, p) walks the segment in blocks of 32
+ * frames and the states in super-blocks of 128: the emission terms of up to
+ * four 32-frame x 32-step tiles (the tile of abcd_pairwise_nll, the prototype's
+ * steps fetched P rows apart) go to LDS, then 128 threads, one state each, run
+ * the recurrence over the block's frames.  The cost plane is never written to
+ * memory.  Tiles wholly outside the band, above s = 2 t or beyond T_proto are
+ * skipped.  States >= T_proto, rows >= L and columns >= F are never read.  The
+ * order of every sum is a function of (len_b, T_proto, F, band) alone: no
+ * atomics, no device-global word, no workgroup waits for another, two calls
+ * agree bit for bit, and a segment scored alone gets the bits of its in-batch
+ * row.  The workspace holds the step offsets.
+ *
+ * abcd_warp_path: the Viterbi programme for ONE prototype per segment,
+ * choice[b] (device, B entries; a value outside 0 .. P - 1 skips the segment,
+ * whose frames are then never read).  state (device, L entries, packed: row
+ * off_t + b) receives a(t), or -1 for a skipped segment and for one no
+ * alignment reaches; path_em / path_off / path_move (B floats each, may be
+ * NULL) the path's sum of e, of o and of -log_move in fp64 (+inf where state
+ * is -1), so that their sum is the path's cost.  One workgroup per segment;
+ * the workspace holds a one-byte back-pointer and the fp32 emission term of
+ * every (t, s) with s < min(T_proto, 2 x->T - 1), and the backtrack runs on
+ * the device in the same launch.
+ *
+ * Limits: x->T <= 4096, B P < 2^31, 1 <= T_proto <= 16383; the workspace
+ * queries return 0 beyond them.  ABCD_EINVAL (checked before any launch,
+ * nothing is written): those limits, a batch_sizes abcd_segment_losses
+ * rejects, P < 1, a stride below F, x->data, gt_offset, proto_mu, proto_lv,
+ * proto_offset_logits or log_move NULL, a NaN or +inf move weight, all three
+ * moves disabled, ld_warp < P, warp (abcd_warp_nll) or choice / state
+ * (abcd_warp_path) NULL, a missing or short workspace.  No timing or dispatch
+ * id is assigned to either entry point.
+ * ---------------------------------------------------------------------- */
+size_t abcd_warp_nll_workspace_bytes(int T, int B, int P, int T_proto);
+int abcd_warp_nll(const abcd_packed* x, const float* gt_offset, int P, int T_proto, const float* proto_mu,
+                  long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                  const double* log_move, int band, int marginal, float* warp, long ld_warp, void* ws,
+                  size_t ws_bytes, void* stream);
+size_t abcd_warp_path_workspace_bytes(int T, int B, int T_proto);
+int abcd_warp_path(const abcd_packed* x, const float* gt_offset, int P, int T_proto, const float* proto_mu,
+                   long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                   const double* log_move, int band, const int32_t* choice, int32_t* state, float* path_em,
+                   float* path_off, float* path_move, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

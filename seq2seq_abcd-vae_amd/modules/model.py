@@ -857,6 +857,67 @@ class RNN_Variational_Decoder(torch.nn.Module):
             lengths = (bs[None, :] > torch.arange(int(bs[0]))[:, None]).sum(1).to(dev)
         return em, (off if gt_off is not None else None), lengths
 
+    def _warp_inputs(self, name, prototypes, batch_sizes, ground_truth_out, ground_truth_offset):
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(ground_truth_out)
+        if not torch.is_tensor(batch_sizes):
+            batch_sizes = torch.tensor([int(b) for b in batch_sizes], dtype=torch.int64)
+        bs = batch_sizes.to("cpu", torch.int64)
+        F = self.rnn_cell.cell.input_size
+        dev = mu.device
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= 1):
+            raise ValueError(f"{name}: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P")
+        gt = _f32c(ground_truth_out.to(dev))
+        if ground_truth_offset is None:  # one on every segment's last frame: packed row off_t + b with t = len_b - 1
+            nxt = torch.cat([bs[1:], bs.new_zeros(1)])
+            gt_off = torch.cat([(torch.arange(int(b)) >= int(n)).float() for b, n in zip(bs.tolist(), nxt.tolist())])
+            gt_off = gt_off.to(dev)
+        else:
+            gt_off = _f32c(ground_truth_offset.to(dev))
+        return gt, bs, gt_off, mu.reshape(-1, F), lv.reshape(-1, F), offl.reshape(-1), int(offl.shape[1]), F
+
+    def warp_against(self, prototypes, batch_sizes, ground_truth_out, ground_truth_offset=None,
+                     log_moves=ops.DEFAULT_LOG_MOVES, band=None, marginal=False):
+        """Every segment time-warped to every prototype: ``warp[b, p]`` (B x P,
+        packed row order), the NLL of segment b under the best alignment of its
+        frames to the steps of prototype p (``marginal=True``: minus the log of
+        the sum over all alignments).  Frame t sits on step a(t), a(0) = 0 and
+        a(t + 1) - a(t) is 0, 1 or 2 (stay, step, skip) at a cost of
+        ``-log_moves[m]`` (-inf disables a move); ``band``: |a(t) - t| <= band.
+        ``prototypes`` is what ``prototypes()`` returned, decoded for any number
+        of steps (shorter or longer than the batch).  With ``log_moves =
+        ops.IDENTITY_LOG_MOVES`` this is ``score_against``'s ``em + off``.
+        ``ground_truth_offset=None``: the end target is one on every segment's
+        last frame.  A pair no alignment reaches gets +inf.  Columns are the
+        prototypes as given: a caller with several speakers' prototypes side
+        by side selects each segment's columns as ``classify.py`` does.
+        Forward-only, under ``torch.no_grad()``."""
+        with torch.no_grad():
+            gt, bs, gt_off, mu, lv, offl, P, F = self._warp_inputs("warp_against", prototypes, batch_sizes,
+                                                                   ground_truth_out, ground_truth_offset)
+            return ops.warp_nll(gt, bs, gt_off, mu, lv, offl, [float(v) for v in log_moves],
+                                -1 if band is None else int(band), bool(marginal), P, F)
+
+    def align_to(self, prototypes, batch_sizes, ground_truth_out, choice, ground_truth_offset=None,
+                 log_moves=ops.DEFAULT_LOG_MOVES, band=None):
+        """The best alignment of every segment to ONE prototype, ``choice[b]``
+        (a column of ``prototypes``; -1 skips the segment): ``(states, em, off,
+        move)`` with ``states`` (L, int32, packed row order: row ``off_t + b``
+        holds a(t)) and the three components of the path's cost per segment,
+        whose sum is ``warp_against``'s entry.  ``states`` is -1, and the
+        components +inf, for a skipped segment and for one no alignment
+        reaches.  Forward-only, under ``torch.no_grad()``."""
+        with torch.no_grad():
+            gt, bs, gt_off, mu, lv, offl, P, F = self._warp_inputs("align_to", prototypes, batch_sizes,
+                                                                   ground_truth_out, ground_truth_offset)
+            choice = torch.as_tensor(choice).to(gt.device, torch.int32)
+            states, em, off, move = ops.warp_path(gt, bs, gt_off, mu, lv, offl, [float(v) for v in log_moves],
+                                                  -1 if band is None else int(band), choice, P, F)
+        return states, em, off, move
+
     def span_scores(self, prototypes, frames, max_length, log_weight=None):
         """Every span of an uncut recording against every prototype:
         ``(span_score, span_cat)``, both ``N + 1 x max_length`` and end-major,

@@ -29,9 +29,11 @@ operator                   replaces (reference)                            C ent
 ``abcd::chain_posterior``  (none: an HMM over category sequences)          ``abcd_chain_posterior``
 ``abcd::span_scores``      (none: every span of an uncut recording)        ``abcd_span_scores``
 ``abcd::span_viterbi``     (none: the best cover by segments)              ``abcd_span_viterbi``
+``abcd::warp_nll``         (none: segments time-warped to prototypes)      ``abcd_warp_nll``
+``abcd::warp_path``        (none: the best alignment and its costs)        ``abcd_warp_path``
 =========================  ==============================================  =========================================
 
-The last eight are forward-only (scoring, synthesis, segmentation): they have no autograd
+The last ten are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -45,6 +47,7 @@ two's-complement int64.
 
 Every operator runs the HIP kernels on the tensors' device; there is no CPU
 kernel (a CPU tensor raises, as everywhere on the product path)."""
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -956,6 +959,115 @@ _forward_only(span_viterbi, "span_viterbi")
 
 
 # ----------------------------------------------------------------------------
+# time-warped scoring: segments aligned to prototypes (forward-only)
+# ----------------------------------------------------------------------------
+DEFAULT_LOG_MOVES = (math.log(0.2), math.log(0.6), math.log(0.2))   # stay, step, skip
+IDENTITY_LOG_MOVES = (-math.inf, 0.0, -math.inf)                    # step only: pairwise_nll's comparison
+
+
+def _warp_args(name, gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, log_moves, band, P, F):
+    """The argument checks warp_nll and warp_path share -> the C call's inputs."""
+    for t in (gt, gt_offset, proto_mu, proto_lv, proto_offset_logits):
+        N.require_gpu(t)
+    P, F = int(P), int(F)
+    if P < 1:
+        raise ValueError(f"{name}: P must be at least 1")
+    lm = [float(v) for v in log_moves]
+    if len(lm) != 3 or any(math.isnan(v) or v == math.inf for v in lm) or all(v == -math.inf for v in lm):
+        raise ValueError(f"{name}: log_moves must be three log weights (stay, step, skip), -inf to disable a move, "
+                         f"at least one enabled; got {lm}")
+    gt = gt.contiguous()
+    (mu, ldm), (lv, ldl) = _rows(proto_mu), _rows(proto_lv)
+    ol = proto_offset_logits.contiguous()
+    gt_offset = gt_offset.contiguous()
+    pk, bs = N.packed(gt, batch_sizes, F)
+    rows = mu.shape[0]
+    if rows % P or rows < P:
+        raise ValueError(f"{name}: the prototype rectangle must hold T_proto * {P} rows with T_proto >= 1, got {rows}")
+    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F) and tuple(gt.shape) == (pk.L, F)):
+        raise ValueError(f"{name}: gt must be {(pk.L, F)}, proto_mu and proto_lv {(rows, F)}")
+    if not (gt_offset.numel() == pk.L and ol.numel() == rows):
+        raise ValueError(f"{name}: gt_offset must hold {pk.L} entries, proto_offset_logits {rows}")
+    moves = (N.c_double * 3)(*lm)
+    return pk, bs, gt, gt_offset, mu, ldm, lv, ldl, ol, rows // P, moves, int(band)
+
+
+@torch.library.custom_op("abcd::warp_nll", mutates_args=())
+def warp_nll(gt: Tensor, batch_sizes: Tensor, gt_offset: Tensor, proto_mu: Tensor, proto_lv: Tensor,
+             proto_offset_logits: Tensor, log_moves: List[float], band: int, marginal: bool, P: int,
+             F: int) -> Tensor:
+    """-> warp (B x P): the time-warped NLL of every segment of the packed batch
+    under every prototype (the rectangle of pairwise_nll; T_proto may be shorter
+    or longer than the batch).  log_moves = log weights of (stay, step, skip),
+    -inf disabling a move; band < 0: no band, else |state - frame| <= band;
+    marginal: -log of the sum over alignments instead of the best one.  +inf
+    where no alignment exists."""
+    pk, bs, gt, gt_offset, mu, ldm, lv, ldl, ol, T_proto, moves, band = _warp_args(
+        "warp_nll", gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, log_moves, band, P, F)
+    L_ = N.lib()
+    nbytes = L_.abcd_warp_nll_workspace_bytes(pk.T, pk.B, int(P), T_proto)
+    if nbytes == 0:
+        raise N.HipError("warp_nll: unsupported shape (more than 4096 steps, more than 16383 prototype steps, "
+                         "or B * P >= 2^31)")
+    ws = N.workspace(nbytes, gt.device)
+    out = torch.empty(pk.B, int(P), device=gt.device)
+    N.check(L_.abcd_warp_nll(pk, N.ptr(gt_offset), int(P), T_proto, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol), moves,
+                             band, int(bool(marginal)), N.ptr(out), int(P), N.ptr(ws), ws.numel(), N.stream()),
+            "warp nll")
+    return out
+
+
+@warp_nll.register_fake
+def _warp_nll_fake(gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, log_moves, band, marginal, P, F):
+    B = int(batch_sizes[0]) if batch_sizes.numel() else 0
+    return gt.new_empty(B, int(P), dtype=torch.float32)
+
+
+_forward_only(warp_nll, "warp_nll")
+
+
+@torch.library.custom_op("abcd::warp_path", mutates_args=())
+def warp_path(gt: Tensor, batch_sizes: Tensor, gt_offset: Tensor, proto_mu: Tensor, proto_lv: Tensor,
+              proto_offset_logits: Tensor, log_moves: List[float], band: int, choice: Tensor, P: int,
+              F: int) -> List[Tensor]:
+    """-> [state (L, int32, packed row order), path_em (B), path_off (B),
+    path_move (B)]: the best alignment of every segment to prototype choice[b]
+    (a choice outside 0 .. P - 1 skips the segment) and the three components of
+    its cost.  state is -1, and the components +inf, for a skipped segment and
+    for one no alignment reaches."""
+    pk, bs, gt, gt_offset, mu, ldm, lv, ldl, ol, T_proto, moves, band = _warp_args(
+        "warp_path", gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, log_moves, band, P, F)
+    N.require_gpu(choice)
+    if choice.numel() != pk.B:
+        raise ValueError(f"warp_path: choice must hold {pk.B} entries, got {choice.numel()}")
+    choice = choice.to(torch.int32).contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_warp_path_workspace_bytes(pk.T, pk.B, T_proto)
+    if nbytes == 0 or pk.B * int(P) >= 2 ** 31:
+        raise N.HipError("warp_path: unsupported shape (more than 4096 steps, more than 16383 prototype steps, "
+                         "or B * P >= 2^31)")
+    dev = gt.device
+    ws = N.workspace(nbytes, dev)
+    state = torch.empty(pk.L, dtype=torch.int32, device=dev)
+    pe, po, pm = (torch.empty(pk.B, device=dev) for _ in range(3))
+    N.check(L_.abcd_warp_path(pk, N.ptr(gt_offset), int(P), T_proto, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol), moves,
+                              band, N.ptr(choice), N.ptr(state), N.ptr(pe), N.ptr(po), N.ptr(pm), N.ptr(ws),
+                              ws.numel(), N.stream()), "warp path")
+    return [state, pe, po, pm]
+
+
+@warp_path.register_fake
+def _warp_path_fake(gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, log_moves, band, choice, P, F):
+    B = int(batch_sizes[0]) if batch_sizes.numel() else 0
+    e = gt.new_empty
+    return [e(gt.shape[0], dtype=torch.int32), e(B, dtype=torch.float32), e(B, dtype=torch.float32),
+            e(B, dtype=torch.float32)]
+
+
+_forward_only(warp_path, "warp_path")
+
+
+# ----------------------------------------------------------------------------
 # log-spectra back to audio (forward-only)
 # ----------------------------------------------------------------------------
 @torch.library.custom_op("abcd::griffin_lim", mutates_args=())
@@ -1009,7 +1121,8 @@ _forward_only(griffin_lim, "griffin_lim")
 
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
-       "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi")
+       "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
+       "warp_nll", "warp_path")
 
 
 def registered() -> Sequence[str]:
