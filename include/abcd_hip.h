@@ -625,6 +625,71 @@ int abcd_span_viterbi(const double* span_score, const int32_t* span_cat, long ld
                       void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Segmentation posteriors: the sum half of the section above (DESIGN.md
+ * s3.12).  S, E and O are those of abcd_span_scores.
+ *
+ * abcd_span_evidence: the pass of abcd_span_scores with the prototypes summed,
+ *   span_lse[e ld_span + d - 1] = log sum_p exp S[e-d, p, d],
+ * over the prototypes abcd_span_scores would not exclude; -inf where nothing is
+ * left and where d > e.  span_score and span_cat may both be NULL; given, they
+ * come out of the same pass and hold the bits abcd_span_scores writes for the
+ * same inputs (all three outputs share ld_span).  Per prototype tile of 32 the
+ * 16 lanes of a start reduce the maximum and then sum_p exp(S - maximum) (the
+ * differences, <= 0, exponentiated in fp32; the maximum, the sum and the
+ * logarithm in fp64) in a fixed shuffle order, and the thread that wrote an
+ * entry folds the later tiles into it with a logaddexp, in tile order: the
+ * ownership rule, the determinism, the limits, the never-read regions, the
+ * workspace and the ABCD_EINVAL rules of abcd_span_scores hold, with span_lse
+ * in span_score's place; span_score NULL and span_cat not, or the reverse, is
+ * ABCD_EINVAL too.
+ *
+ * abcd_span_posterior: the semi-Markov forward-backward over one recording in
+ * fp64.  span is a table laid out as span_score (the maximum or the sum: the
+ * programme does not care), gap / seg_bonus / d_min are those of
+ * abcd_span_viterbi.  A candidate that is NaN or -inf is excluded; LAE is
+ * logaddexp, LSE the log-sum-exp over the admissible candidates, -inf over none:
+ *   a[0] = 0, aseg[0] = -inf;  n = 1 .. N:
+ *     aseg[n] = seg_bonus + LSE_{d_min <= d <= min(D,n)} (a[n-d] + span[n,d])
+ *     a[n]    = LAE(a[n-1] + gap[n-1], aseg[n])
+ *   b[N] = 0, bseg[N] = -inf;  n = N-1 .. 0:
+ *     bseg[n] = LSE_{d_min <= d <= min(D,N-n)} (span[n+d,d] + seg_bonus + b[n+d])
+ *     b[n]    = LAE(gap[n] + b[n+1], bseg[n])
+ *   log_z = a[N]
+ *   post[n]             = exp(a[n] + bseg[n] - log_z), n < N      a segment starts at frame n
+ *   post[N+1 + n]       = exp(aseg[n] + b[n] - log_z), n >= 1     a segment ends before frame n
+ *   post[2 (N+1) + n]   = exp(a[n] + gap[n] + b[n+1] - log_z), n < N   frame n is background
+ *   span_post[e ld_post + d - 1] = exp(a[e-d] + span[e,d] + seg_bonus + b[e] - log_z)
+ * and 0 elsewhere (post is 3 x (N + 1), span_post N + 1 rows with ld_post >=
+ * D, zero outside d_min .. min(D, e)); log_z = -inf (no cover) makes every
+ * posterior 0.  lattice (4 x (N + 1): a, aseg, b, bseg) and span_post may be
+ * NULL.  One workgroup runs both sweeps and the per-frame posteriors in one
+ * launch; the backward sweep walks the ENDS e = N .. 1 and folds span[e,d] +
+ * seg_bonus + b[e] into a ring slot per start, so it reads the same contiguous
+ * rows as the forward sweep.  span_post comes from a second, ordinary kernel,
+ * launched only when asked for.  No atomics, no device-global word, nothing is
+ * allocated, two calls agree bit for bit.  A table that holds +inf is outside
+ * the contract (the result is unspecified; nothing outside the arguments is
+ * touched).  The workspace holds the lattice when the caller keeps none.
+ * Limits: those of abcd_span_viterbi; the workspace query returns 0 beyond
+ * them.  ABCD_EINVAL (checked before any launch, nothing is written): d_min < 1
+ * or d_min > D, ld_span < D, ld_post < D with span_post given, span, log_z or
+ * post NULL while N > 0, a missing or short workspace.  N = 0 writes log_z = 0
+ * (and a = b = 0, aseg = bseg = -inf, zero posteriors, each where not NULL) and
+ * reads nothing.
+ *
+ * No timing or dispatch id is assigned to either entry point.
+ * ---------------------------------------------------------------------- */
+size_t abcd_span_evidence_workspace_bytes(long N, int D, int P);
+int abcd_span_evidence(const float* x, long ld_x, long N, int F, int P, int D, int T_proto, const float* proto_mu,
+                       long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                       const float* log_weight, double* span_lse, double* span_score, int32_t* span_cat,
+                       long ld_span, void* ws, size_t ws_bytes, void* stream);
+size_t abcd_span_posterior_workspace_bytes(long N, int D);
+int abcd_span_posterior(const double* span, long ld_span, long N, int D, int d_min, const float* gap,
+                        double seg_bonus, double* log_z, double* lattice, double* post, double* span_post,
+                        long ld_post, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Time-warped scoring: a segment aligned to a prototype.  abcd_pairwise_nll
  * scores frame t against step t; here the T_proto steps of prototype p are the
  * states of a left-to-right HMM and frame t of segment b is emitted by state

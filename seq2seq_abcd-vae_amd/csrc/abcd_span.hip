@@ -13,6 +13,11 @@
 //                 prototype per (s, d) folded into the end-major output
 //   span_viterbi  one workgroup: the semi-Markov dynamic programme over the
 //                 output of span_nll and the backtrack
+//   span_nll<true>  the same pass with the log-sum over the prototypes beside
+//                 (or instead of) the maximum (abcd_span_evidence, s3.12)
+//   span_fb       one workgroup: the sum form of span_viterbi, forward and
+//                 backward over one recording, and the per-frame posteriors
+//   span_post_table  the per-span posteriors from the lattice, many workgroups
 //
 // span_nll runs on the emission tile pair_nll runs on (abcd_emtile.h: the
 // staging, the per-term expressions and the order of a frame's sums, F columns
@@ -47,15 +52,29 @@ __global__ __launch_bounds__(256) void span_prefix(const float* __restrict__ OL,
 }
 
 // rows e <= min(N, D - 1): the entries with d > e
+// (span_lse, and span_score with span_cat, each where not NULL)
 __global__ __launch_bounds__(256) void span_fill(long rows, int D, double* __restrict__ span_score,
-                                                 int32_t* __restrict__ span_cat, long lds) {
+                                                 int32_t* __restrict__ span_cat, double* __restrict__ span_lse,
+                                                 long lds) {
   const long at = (long)blockIdx.x * 256 + threadIdx.x;
   if (at >= rows * D) return;
   const long e = at / D;
   const int c = (int)(at - e * D);  // d - 1
   if (c < e) return;
-  span_score[e * lds + c] = -INFINITY;
-  span_cat[e * lds + c] = -1;
+  if (span_score) {
+    span_score[e * lds + c] = -INFINITY;
+    span_cat[e * lds + c] = -1;
+  }
+  if (span_lse) span_lse[e * lds + c] = -INFINITY;
+}
+
+// log(e^a + e^b) in fp64; -inf when neither is above -inf (NaN counts as -inf)
+DEV double logaddexp_d(double a, double b) {
+  const bool va = a > -INFINITY, vb = b > -INFINITY;
+  if (!va) return vb ? b : -INFINITY;
+  if (!vb) return a;
+  const double hi = fmax(a, b), lo = fmin(a, b);
+  return hi + log1p(exp(lo - hi));
 }
 
 // Workgroup blockIdx.x owns starts s0 = 32 blockIdx.x .. s0 + 31 and every
@@ -70,12 +89,22 @@ __global__ __launch_bounds__(256) void span_fill(long rows, int D, double* __res
 // the result into the output entry: a plain store for the first prototype
 // tile, a read and a strict comparison for the later ones (the same thread
 // wrote what it reads).  Rows >= N and steps >= D are not read.
+//
+// LSE (abcd_span_evidence) adds the log-sum over the same admissible
+// prototypes: the 16 lanes reduce the maximum m (the one the argmax tree just
+// found) and then sum_p exp(S - m), the differences exponentiated in fp32 and
+// summed in fp64 in a fixed shuffle order; lane j = i (i = 0, 1: the thread's
+// two starts, so the two logarithms of a step run side by side) writes m + log
+// sum for the first prototype tile and folds later tiles into what it wrote
+// with a logaddexp.  The maximum's code is the same statements in both
+// instantiations, span_score / span_cat may be NULL in this one.
+template <bool LSE>
 __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, long ldx, long N, int F, int P, int D,
                                                 const float* __restrict__ MU, long ldm,
                                                 const float* __restrict__ LV, long ldl,
                                                 const double* __restrict__ Otab, const float* __restrict__ LW,
                                                 double* __restrict__ span_score, int32_t* __restrict__ span_cat,
-                                                long lds) {
+                                                double* __restrict__ span_lse, long lds) {
   __shared__ EmTile tile;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const long s0 = (long)blockIdx.x * EM_TR;
@@ -110,6 +139,7 @@ __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, lon
       if (last) {  // the frame is complete: one fp32 value per (start, prototype) joins the fp64 sum
         const float c0 = tile.cs[k][tj], c1 = tile.cs[k][tj + 16];
         const double oa = pa < P ? Otab[(long)t * P + pa] : 0.0, ob = pb < P ? Otab[(long)t * P + pb] : 0.0;
+        double tm[2], tsum[2];  // LSE: the tile's maximum and sum_p exp(S - maximum) of the thread's two starts
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
           const long e = s0 + 2 * ti + i + t + 1;  // the end of start s0 + 2 ti + i at length t + 1
@@ -123,9 +153,18 @@ __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, lon
           int arg = pa, ab = pb;
           if (!(sa > -INFINITY)) { sa = -INFINITY; arg = INT_MAX; }  // NaN and -inf: excluded
           if (!(sb > -INFINITY)) { sb = -INFINITY; ab = INT_MAX; }
+          const double ua = sa, ub = sb;
           if (sb > sa) { sa = sb; arg = ab; }
           wave_argmax<16>(sa, arg);  // the 16 lanes of one start
-          if (tj == 0 && v) {
+          if (LSE) {
+            double z = 0.0;  // an excluded prototype adds nothing; sa = -inf leaves every term out
+            if (ua > -INFINITY) z += (double)__expf((float)(ua - sa));
+            if (ub > -INFINITY) z += (double)__expf((float)(ub - sa));
+            for (int o = 8; o > 0; o >>= 1) z += __shfl_xor(z, o, 64);
+            tm[i] = sa;
+            tsum[i] = z;
+          }
+          if (tj == 0 && v && (!LSE || span_score)) {
             const long at = e * lds + t;
             if (p0 == 0) {
               span_score[at] = sa;
@@ -134,6 +173,15 @@ __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, lon
               span_score[at] = sa;
               span_cat[at] = arg;
             }
+          }
+        }
+        if (LSE && tj < 2) {
+          const long e = s0 + 2 * ti + tj + t + 1;
+          if (e <= N) {
+            const double m = tj ? tm[1] : tm[0], z = tj ? tsum[1] : tsum[0];
+            const double here = m > -INFINITY ? m + log(z) : -INFINITY;
+            const long at = e * lds + t;
+            span_lse[at] = p0 == 0 ? here : logaddexp_d(span_lse[at], here);
           }
         }
       }
@@ -270,6 +318,227 @@ __global__ __launch_bounds__(SV_THREADS) void span_viterbi(const double* __restr
   *path_score = vprev;
 }
 
+// The sum form of span_viterbi: one workgroup, one launch,
+// the same launch widths, row prefetch and ring.  lat holds alpha, alpha_seg,
+// beta, beta_seg, N + 1 doubles each.
+//
+// Forward, n = 1 .. N: the candidates alpha[n-d] + W[n,d] as in span_viterbi
+// (four per thread from registers, the rest in a loop); their maximum over the
+// thread, a wave shuffle tree and the waves in order; then each candidate's
+// exp(c - maximum), summed the same way: one exp per candidate, one log per
+// step.  Every thread forms alpha[n] itself, so d = 1 comes from a register
+// and thread 0's ring store is first read two barriers later.
+//
+// Backward, e = N .. 0, over ENDS: beta_seg[s] = LSE_d (W[s+d,d] + bonus +
+// beta[s+d]) reads an anti-diagonal of the end-major table, so the sweep walks
+// the rows instead and thread d folds W[e,d] + bonus + beta[e] into the slot
+// of start e - d with a logaddexp.  The ring has D + 1 slots, start s at s mod
+// (D + 1): at step e the slots e-1 .. e-D are written, each by one thread, and
+// slot e, complete since step e + 1, is only read, so one barrier per step
+// orders everything.  The thread with d = D is the first to reach its start and
+// starts from an empty slot; starts within D of the end find the empty slots
+// the ring was filled with.  PAIR: a slot is (maximum, sum of exp(c - maximum)),
+// the sums in a second ring behind the first, so a fold costs one exp and the
+// logarithm is taken once per start, when the slot is read; it measured 24 %
+// under the whole launch with log-domain slots (a logaddexp, exp and log1p, per
+// fold) and is used while both rings fit the LDS the widest
+// span_viterbi ring takes, D <= SF_PAIR_MAX_D.
+//
+// Then log_z = alpha[N] and the per-frame posteriors, elementwise from the
+// lattice this workgroup wrote (a barrier apart).
+constexpr int SF_PAIR_MAX_D = (SP_MAX_D + 1) / 2 - 1;  // 8191: 2 (D + 1) doubles in 128 KB
+
+template <bool PAIR>
+__global__ __launch_bounds__(SV_THREADS) void span_fb(const double* __restrict__ W, long ldw, long N, int D, int dmin,
+                                                      const float* __restrict__ gap, double bonus, double* log_z,
+                                                      double* lat, double* post) {
+  extern __shared__ __attribute__((aligned(16))) double ring[];  // D + 1 slots (PAIR: twice)
+  __shared__ double wm[SV_THREADS / 64], wz[SV_THREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nt = blockDim.x, nw = nt >> 6;
+  double* const A = lat;
+  double* const AS = lat + (N + 1);
+  double* const B = lat + 2 * (N + 1);
+  double* const BS = lat + 3 * (N + 1);
+  double pre[SV_PRE];
+  float gnext = 0.f;
+  auto load_row = [&](long n, long g) {  // row n of the table and gap[g] (g >= 0), both one step ahead of their use
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) {
+      const int d = tid + 1 + nt * r;
+      pre[r] = W[n * ldw + min(d, D) - 1];
+    }
+    if (gap && g >= 0) gnext = gap[g];
+  };
+  // ---- forward
+  if (tid == 0) {
+    ring[0] = 0.0;
+    A[0] = 0.0;
+    AS[0] = -INFINITY;
+  }
+  __syncthreads();
+  double vprev = 0.0;
+  if (N >= 1) load_row(1, 0);
+  int pos = 0;  // (n - 1) mod D
+  for (long n = 1; n <= N; ++n) {
+    double cur[SV_PRE];
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) cur[r] = pre[r];
+    const double gapc = gap ? vprev + (double)gnext : -INFINITY;
+    if (n < N) load_row(n + 1, n);
+    pos = pos + 1 == D ? 0 : pos + 1;  // n mod D
+    const int dmax = (int)min((long)D, n);
+    double m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) {
+      const int d = tid + 1 + nt * r;
+      int at = pos - min(d, D);
+      at += at < 0 ? D : 0;
+      const double v = ring[at];  // a slot not written yet (d > n) is read and masked
+      const double c = (d == 1 ? vprev : v) + cur[r];
+      cur[r] = ((d >= dmin) & (d <= dmax) & (c > -INFINITY)) ? c : -INFINITY;  // NaN and -inf: excluded
+      m = fmax(m, cur[r]);
+    }
+    for (int d = tid + 1 + nt * SV_PRE; d <= dmax; d += nt) {
+      if (d < dmin) continue;
+      int at = pos - d;
+      if (at < 0) at += D;
+      const double c = ring[at] + W[n * ldw + d - 1];
+      if (c > m) m = c;
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+    if (lane == 0) wm[w] = m;
+    __syncthreads();
+    m = wm[0];
+    for (int i = 1; i < nw; ++i) m = fmax(m, wm[i]);
+    double z = 0.0;
+    if (m > -INFINITY) {
+#pragma unroll
+      for (int r = 0; r < SV_PRE; ++r) z += cur[r] > -INFINITY ? exp(cur[r] - m) : 0.0;
+      for (int d = tid + 1 + nt * SV_PRE; d <= dmax; d += nt) {
+        if (d < dmin) continue;
+        int at = pos - d;
+        if (at < 0) at += D;
+        const double c = ring[at] + W[n * ldw + d - 1];  // the same two operands as in the pass above
+        if (c > -INFINITY) z += exp(c - m);
+      }
+    }
+    z = wave_sum_d(z);
+    if (lane == 0) wz[w] = z;
+    __syncthreads();
+    z = wz[0];
+    for (int i = 1; i < nw; ++i) z += wz[i];
+    const double aseg = m > -INFINITY ? bonus + (m + log(z)) : -INFINITY;
+    const double a = logaddexp_d(gapc, aseg);
+    vprev = a;
+    if (tid == 0) {
+      ring[pos] = a;
+      A[n] = a;
+      AS[n] = aseg;
+    }
+  }
+  // ---- backward
+  __syncthreads();
+  const int R = D + 1;
+  double* const ring2 = ring + R;  // PAIR: the sums
+  for (int i = tid; i < R; i += nt) {
+    ring[i] = -INFINITY;
+    if (PAIR) ring2[i] = 0.0;
+  }
+  auto fold = [&](int at, int d, double c) {  // candidate c (-inf: none) of length d into the slot of its start
+    double mo = ring[at], zo = PAIR ? ring2[at] : 0.0;
+    if (d == D) { mo = -INFINITY; zo = 0.0; }  // the first to reach this start: the slot's earlier start is done
+    if (PAIR) {
+      if (c > -INFINITY) {
+        const double w = exp(-fabs(mo - c));  // mo = -inf: 0
+        if (c > mo) { zo = zo * w + 1.0; mo = c; } else zo += w;
+      }
+      ring[at] = mo;
+      ring2[at] = zo;
+    } else {
+      ring[at] = logaddexp_d(mo, c);
+    }
+  };
+  if (N >= 1) load_row(N, -1);  // step e uses row e and gap[e]; step N has no gap
+  double bnext = 0.0;
+  int slot = (int)(N % R);  // e mod (D + 1)
+  for (long e = N; e >= 0; --e) {
+    double cur[SV_PRE];
+#pragma unroll
+    for (int r = 0; r < SV_PRE; ++r) cur[r] = pre[r];
+    const float gnow = gnext;
+    if (e >= 1) load_row(e - 1, e - 1);  // row 0 exists (all -inf) and is not used
+    __syncthreads();
+    double b = 0.0, bseg = -INFINITY;
+    if (e < N) {
+      bseg = ring[slot];
+      if (PAIR) bseg = bseg > -INFINITY ? bseg + log(ring2[slot]) : -INFINITY;
+      b = logaddexp_d(gap ? (double)gnow + bnext : -INFINITY, bseg);
+    }
+    bnext = b;
+    if (tid == 0) {
+      B[e] = b;
+      BS[e] = bseg;
+    }
+    if (e >= 1) {
+      const int dmax = (int)min((long)D, e);
+#pragma unroll
+      for (int r = 0; r < SV_PRE; ++r) {
+        const int d = tid + 1 + nt * r;
+        if (d <= dmax) {
+          int at = slot - d;
+          at += at < 0 ? R : 0;
+          double c = (cur[r] + bonus) + b;
+          if (!((d >= dmin) & (c > -INFINITY))) c = -INFINITY;
+          fold(at, d, c);
+        }
+      }
+      for (int d = tid + 1 + nt * SV_PRE; d <= dmax; d += nt) {
+        int at = slot - d;
+        if (at < 0) at += R;
+        double c = (W[e * ldw + d - 1] + bonus) + b;
+        if (!((d >= dmin) & (c > -INFINITY))) c = -INFINITY;
+        fold(at, d, c);
+      }
+    }
+    slot = slot == 0 ? R - 1 : slot - 1;
+  }
+  // ---- log_z and the per-frame posteriors
+  __syncthreads();
+  const double lz = A[N];
+  if (tid == 0 && log_z) *log_z = lz;
+  if (!post) return;
+  const bool reach = lz > -INFINITY;
+  for (long n = tid; n <= N; n += nt) {
+    double on = 0.0, en = 0.0, gp = 0.0;
+    if (reach) {
+      if (n < N) on = exp(A[n] + BS[n] - lz);
+      if (n >= 1) en = exp(AS[n] + B[n] - lz);
+      if (n < N && gap) gp = exp(A[n] + (double)gap[n] + B[n + 1] - lz);
+    }
+    post[n] = on > 0.0 ? on : 0.0;  // a NaN (inf - inf, outside the contract) reads as 0
+    post[(N + 1) + n] = en > 0.0 ? en : 0.0;
+    post[2 * (N + 1) + n] = gp > 0.0 ? gp : 0.0;
+  }
+}
+
+// span_post[e, d - 1] = exp(alpha[e-d] + W[e,d] + bonus + beta[e] - log_z), 0 outside d_min .. min(D, e)
+__global__ __launch_bounds__(256) void span_post_table(const double* __restrict__ W, long ldw, long N, int D, int dmin,
+                                                       double bonus, const double* __restrict__ lat,
+                                                       double* __restrict__ span_post, long ldp) {
+  const long at = (long)blockIdx.x * 256 + threadIdx.x;
+  if (at >= (N + 1) * D) return;
+  const long e = at / D;
+  const int d = (int)(at - e * D) + 1;
+  const double lz = lat[N];
+  double v = 0.0;
+  if (d >= dmin && d <= e && lz > -INFINITY) {
+    const double c = ((lat[e - d] + W[e * ldw + d - 1]) + bonus) + lat[2 * (N + 1) + e];
+    if (c > -INFINITY) v = exp(c - lz);
+  }
+  span_post[e * ldp + d - 1] = v > 0.0 ? v : 0.0;
+}
+
 static bool span_shape_ok(long N, int D) {
   return D >= 1 && D <= SP_MAX_D && N >= 0 && N < (1L << 31) && (N + 1) * (long)D < (1L << 31);
 }
@@ -295,13 +564,42 @@ extern "C" int abcd_span_scores(const float* x, long ld_x, long N, int F, int P,
   if (!span_score || !span_cat) return 0;  // N = 0 with nowhere to write row 0
   hipStream_t s = (hipStream_t)stream;
   const long rows = std::min(N, (long)D - 1) + 1;
-  span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, ld_span);
+  span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, nullptr, ld_span);
   ABCD_CHECK_LAUNCH();
   if (N == 0) return 0;
   double* Otab = (double*)ws;
   span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab, log_weight,
-                                          span_score, span_cat, ld_span);
+  span_nll<false><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+                                                 log_weight, span_score, span_cat, nullptr, ld_span);
+  ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t abcd_span_evidence_workspace_bytes(long N, int D, int P) {
+  return abcd_span_scores_workspace_bytes(N, D, P);
+}
+
+extern "C" int abcd_span_evidence(const float* x, long ld_x, long N, int F, int P, int D, int T_proto,
+                                  const float* proto_mu, long ld_mu, const float* proto_lv, long ld_lv,
+                                  const float* proto_offset_logits, const float* log_weight, double* span_lse,
+                                  double* span_score, int32_t* span_cat, long ld_span, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  ABCD_REQUIRE(span_shape_ok(N, D) && P >= 1 && F >= 1 && T_proto >= D);
+  ABCD_REQUIRE(ld_x >= F && ld_mu >= F && ld_lv >= F && ld_span >= D);
+  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits && span_lse));
+  ABCD_REQUIRE(!span_score == !span_cat);  // the best outputs come together or not at all
+  const size_t need = abcd_span_evidence_workspace_bytes(N, D, P);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  if (!span_lse && !span_score) return 0;  // N = 0 with nowhere to write row 0
+  hipStream_t s = (hipStream_t)stream;
+  const long rows = std::min(N, (long)D - 1) + 1;
+  span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, span_lse, ld_span);
+  ABCD_CHECK_LAUNCH();
+  if (N == 0) return 0;
+  double* Otab = (double*)ws;
+  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
+  span_nll<true><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+                                                log_weight, span_score, span_cat, span_lse, ld_span);
   ABCD_CHECK_LAUNCH();
   return 0;
 }
@@ -337,5 +635,44 @@ extern "C" int abcd_span_viterbi(const double* span_score, const int32_t* span_c
                                                                  seg_bonus, path_score, n_segments, seg_onset,
                                                                  seg_length, seg_cat, seg_score, V_out, (int32_t*)ws);
   ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t abcd_span_posterior_workspace_bytes(long N, int D) {
+  if (!span_shape_ok(N, D)) return 0;
+  return 4 * ((size_t)N + 1) * sizeof(double) + 256;  // the lattice when the caller keeps none
+}
+
+extern "C" int abcd_span_posterior(const double* span, long ld_span, long N, int D, int d_min, const float* gap,
+                                   double seg_bonus, double* log_z, double* lattice, double* post, double* span_post,
+                                   long ld_post, void* ws, size_t ws_bytes, void* stream) {
+  ABCD_REQUIRE(span_shape_ok(N, D) && d_min >= 1 && d_min <= D && ld_span >= D);
+  ABCD_REQUIRE(!span_post || ld_post >= D);
+  ABCD_REQUIRE(N == 0 || (span && log_z && post));
+  const size_t need = abcd_span_posterior_workspace_bytes(N, D);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  if (!log_z && !lattice && !post && !span_post) return 0;  // N = 0 with nowhere to write
+  hipStream_t s = (hipStream_t)stream;
+  static bool attr = false;
+  if (!attr) {
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_fb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (SP_MAX_D + 1) * (int)sizeof(double)));
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_fb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (SP_MAX_D + 1) * (int)sizeof(double)));
+    attr = true;
+  }
+  double* lat = lattice ? lattice : (double*)ws;
+  const int threads = D <= SV_ONE_WAVE_D ? 64 : SV_THREADS;
+  const size_t slots = ((size_t)D + 1) * sizeof(double);
+  if (D <= SF_PAIR_MAX_D)
+    span_fb<true><<<1, threads, 2 * slots, s>>>(span, ld_span, N, D, d_min, gap, seg_bonus, log_z, lat, post);
+  else
+    span_fb<false><<<1, threads, slots, s>>>(span, ld_span, N, D, d_min, gap, seg_bonus, log_z, lat, post);
+  ABCD_CHECK_LAUNCH();
+  if (span_post) {
+    span_post_table<<<cdiv((N + 1) * D, 256), 256, 0, s>>>(span, ld_span, N, D, d_min, seg_bonus, lat, span_post,
+                                                           ld_post);
+    ABCD_CHECK_LAUNCH();
+  }
   return 0;
 }

@@ -945,6 +945,31 @@ class RNN_Variational_Decoder(torch.nn.Module):
                                          log_weight, P, D)
         return score, cat
 
+    def span_evidence(self, prototypes, frames, max_length, log_weight=None, want_best=False):
+        """``span_scores`` with the prototypes summed instead of maximised:
+        ``(span_lse, span_score, span_cat)`` with ``span_lse[e, d - 1]``
+        (float64, ``N + 1 x max_length``, end-major) the log of the sum over
+        the prototypes p of ``exp(log_weight[p] - em - off)`` for frames ``e -
+        d .. e - 1`` -- with normalised weights the log-likelihood of the span
+        being one segment of any category.  With ``want_best`` the same pass
+        also returns ``span_scores``' two tables, bit for bit; without it they
+        are None.  Forward-only, under ``torch.no_grad()``."""
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(frames)
+        F, D = self.rnn_cell.cell.input_size, int(max_length)
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= D >= 1):
+            raise ValueError(f"span_evidence: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
+        if frames.dim() != 2 or frames.shape[1] != F:
+            raise ValueError(f"span_evidence: frames must be N x {F}, got {tuple(frames.shape)}")
+        P = int(offl.shape[1])
+        with torch.no_grad():
+            lse, score, cat = ops.span_evidence(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F),
+                                                offl.reshape(-1), log_weight, P, D, bool(want_best))
+        return (lse, score, cat) if want_best else (lse, None, None)
+
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()
         return torch.tensor([int((lengths > t).sum()) for t in range(int(lengths.max()))], dtype=torch.int64)

@@ -31,9 +31,11 @@ operator                   replaces (reference)                            C ent
 ``abcd::span_viterbi``     (none: the best cover by segments)              ``abcd_span_viterbi``
 ``abcd::warp_nll``         (none: segments time-warped to prototypes)      ``abcd_warp_nll``
 ``abcd::warp_path``        (none: the best alignment and its costs)        ``abcd_warp_path``
+``abcd::span_evidence``    (none: span scores summed over the categories)  ``abcd_span_evidence``
+``abcd::span_posterior``   (none: posteriors over all covers by segments)  ``abcd_span_posterior``
 =========================  ==============================================  =========================================
 
-The last ten are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
+The last twelve are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -958,6 +960,114 @@ def _(span_score, span_cat, d_min, gap, seg_bonus, want_v):
 _forward_only(span_viterbi, "span_viterbi")
 
 
+@torch.library.custom_op("abcd::span_evidence", mutates_args=())
+def span_evidence(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_logits: Tensor,
+                  log_weight: Optional[Tensor], P: int, D: int, want_best: bool) -> List[Tensor]:
+    """-> [span_lse (N + 1 x D, fp64), span_score, span_cat]: span_scores' pass
+    with the prototypes summed, entry [e, d - 1] the log of the sum over the
+    admissible prototypes of exp(log_weight[p] - em - off) for frames e - d ..
+    e - 1 (abcd_span_evidence).  With want_best the same pass also gives
+    span_scores' two tables, bit for bit; without it they are 0 x 0."""
+    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
+        N.require_gpu(t)
+    P, D = int(P), int(D)
+    if frames.dim() != 2 or frames.shape[1] < 1:
+        raise ValueError(f"span_evidence: frames must be N x F, got {tuple(frames.shape)}")
+    n, F = (int(v) for v in frames.shape)
+    if P < 1 or D < 1:
+        raise ValueError("span_evidence: P and D must be at least 1")
+    dev = frames.device
+    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
+    ol = proto_offset_logits.float().contiguous()
+    rows = int(ol.numel())
+    if rows % P or rows // P < D:
+        raise ValueError(f"span_evidence: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
+                         f"got {rows}")
+    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
+        raise ValueError(f"span_evidence: proto_mu and proto_lv must be {(rows, F)}")
+    lw = None
+    if log_weight is not None:
+        N.require_gpu(log_weight)
+        if log_weight.numel() != P:
+            raise ValueError(f"span_evidence: log_weight must hold {P} entries, got {log_weight.numel()}")
+        lw = log_weight.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_span_evidence_workspace_bytes(n, D, P)
+    if nbytes == 0:
+        raise N.HipError("span_evidence: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
+    ws = N.workspace(nbytes, dev)
+    lse = torch.empty(n + 1, D, dtype=torch.float64, device=dev)
+    shape = (n + 1, D) if want_best else (0, 0)
+    score = torch.empty(shape, dtype=torch.float64, device=dev)
+    cat = torch.empty(shape, dtype=torch.int32, device=dev)
+    N.check(L_.abcd_span_evidence(N.ptr(x), ldx, n, F, P, D, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                                  N.ptr(lw), N.ptr(lse), N.ptr(score) if want_best else None,
+                                  N.ptr(cat) if want_best else None, D, N.ptr(ws), ws.numel(), N.stream()),
+            "span evidence")
+    return [lse, score, cat]
+
+
+@span_evidence.register_fake
+def _(frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D, want_best):
+    n = frames.shape[0]
+    shape = (n + 1, int(D)) if want_best else (0, 0)
+    return [frames.new_empty(n + 1, int(D), dtype=torch.float64), frames.new_empty(shape, dtype=torch.float64),
+            frames.new_empty(shape, dtype=torch.int32)]
+
+
+_forward_only(span_evidence, "span_evidence")
+
+
+@torch.library.custom_op("abcd::span_posterior", mutates_args=())
+def span_posterior(span: Tensor, d_min: int, gap: Optional[Tensor], seg_bonus: float,
+                   want_table: bool) -> List[Tensor]:
+    """-> [log_z (0-d, fp64), lattice (4 x (N + 1): alpha, alpha_seg, beta,
+    beta_seg), post (3 x (N + 1): onset, end, gap posteriors), span_post (N + 1
+    x D, or 0 x 0)]: the semi-Markov forward-backward over span_scores' or
+    span_evidence's table (N + 1 x D; row-strided views pass without a copy)
+    under span_viterbi's d_min, gap and seg_bonus, abcd_span_posterior.  An
+    unreachable end gives log_z = -inf and zero posteriors."""
+    N.require_gpu(span)
+    if span.dim() != 2 or span.shape[0] < 1 or span.shape[1] < 1:
+        raise ValueError(f"span_posterior: span must be N + 1 x D, got {tuple(span.shape)}")
+    n, D = int(span.shape[0]) - 1, int(span.shape[1])
+    d_min = int(d_min)
+    if d_min < 1 or d_min > D:
+        raise ValueError(f"span_posterior: d_min must lie in 1 .. {D}, got {d_min}")
+    dev = span.device
+    ss, ld = _rows(span.double())
+    g = None
+    if gap is not None:
+        N.require_gpu(gap)
+        if gap.numel() != n:
+            raise ValueError(f"span_posterior: gap must hold {n} entries, got {gap.numel()}")
+        g = gap.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_span_posterior_workspace_bytes(n, D)
+    if nbytes == 0:
+        raise N.HipError("span_posterior: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
+    ws = N.workspace(nbytes, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    log_z = torch.empty((), **f64)
+    lattice, post = torch.empty(4, n + 1, **f64), torch.empty(3, n + 1, **f64)
+    table = torch.empty((n + 1, D) if want_table else (0, 0), **f64)
+    N.check(L_.abcd_span_posterior(N.ptr(ss), ld, n, D, d_min, N.ptr(g), float(seg_bonus), N.ptr(log_z),
+                                   N.ptr(lattice), N.ptr(post), N.ptr(table) if want_table else None, D, N.ptr(ws),
+                                   ws.numel(), N.stream()), "span posterior")
+    return [log_z, lattice, post, table]
+
+
+@span_posterior.register_fake
+def _(span, d_min, gap, seg_bonus, want_table):
+    n = span.shape[0] - 1
+    e = span.new_empty
+    return [e((), dtype=torch.float64), e((4, n + 1), dtype=torch.float64), e((3, n + 1), dtype=torch.float64),
+            e((n + 1, span.shape[1]) if want_table else (0, 0), dtype=torch.float64)]
+
+
+_forward_only(span_posterior, "span_posterior")
+
+
 # ----------------------------------------------------------------------------
 # time-warped scoring: segments aligned to prototypes (forward-only)
 # ----------------------------------------------------------------------------
@@ -1122,7 +1232,7 @@ _forward_only(griffin_lim, "griffin_lim")
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
        "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
-       "warp_nll", "warp_path")
+       "warp_nll", "warp_path", "span_evidence", "span_posterior")
 
 
 def registered() -> Sequence[str]:

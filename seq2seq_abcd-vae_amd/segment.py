@@ -44,6 +44,8 @@ import cli
 from modules import _native, segmentation
 
 COLUMNS = ("onset", "offset", "input_path", "data_type", "speaker", "label", "category_ix", "length", "segment_score")
+POSTERIOR_COLUMNS = ("onset_posterior", "offset_posterior", "span_posterior")   # appended by --posteriors
+RECORDING_COLUMNS = ("input_path", "n_frames", "n_segments", "path_score", "log_evidence", "expected_segments")
 
 
 def num_frames(samples, frame, hop, centering=True):
@@ -89,24 +91,40 @@ def covered_frames(n_frames, onsets, offsets, fs, frame, hop, centering=True):
 
 
 def segment_rows(input_path, onset, length, category, score, fs, frame, hop, centering, total, data_type="segmented",
-                 speaker=float("nan")):
-    """The table rows of one recording's segments (frame units -> seconds)."""
+                 speaker=float("nan"), posteriors=None):
+    """The table rows of one recording's segments (frame units -> seconds);
+    ``posteriors``: the three per-segment lists of POSTERIOR_COLUMNS."""
     rows = []
-    for s, d, k, v in zip(onset, length, category, score):
+    for i, (s, d, k, v) in enumerate(zip(onset, length, category, score)):
         on, off = frames_to_samples(s, d, frame, hop, centering, total)
         rows.append({"onset": on / fs, "offset": off / fs, "input_path": input_path, "data_type": data_type,
                      "speaker": speaker, "label": int(k), "category_ix": int(k), "length": int(d),
                      "segment_score": float(v)})
+        if posteriors is not None:
+            rows[-1].update({c: float(p[i]) for c, p in zip(POSTERIOR_COLUMNS, posteriors)})
     return rows
 
 
-def write_segments(save_path, rows):
+def write_segments(save_path, rows, posteriors=False, recordings_out=None, recordings=(), curves=None):
     """Writes the annotation table (an existing file is kept as .prev, nothing
-    partial is left behind).  Returns the number of rows."""
-    df = pd.DataFrame(rows, columns=list(COLUMNS))
+    partial is left behind) and, with ``posteriors``, its three extra columns,
+    the per-recording table and the per-recording curve files ({path: dict of
+    arrays}) in the same replacement.  Returns the number of rows."""
+    df = pd.DataFrame(rows, columns=list(COLUMNS) + (list(POSTERIOR_COLUMNS) if posteriors else []))
     with cli.replacing_outputs() as tmp:
         df.to_csv(tmp(save_path), index=False)
+        if recordings_out is not None:
+            pd.DataFrame(list(recordings), columns=list(RECORDING_COLUMNS)).to_csv(tmp(recordings_out), index=False)
+        for path, arrays in (curves or {}).items():
+            with open(tmp(path), "wb") as f:
+                np.savez(f, **arrays)
     return len(df)
+
+
+def curve_path(curves_dir, input_path):
+    """<curves_dir>/<the recording's path with separators replaced, without its extension>.npz"""
+    stem = os.path.splitext(input_path)[0].replace(os.sep, "__").replace("/", "__")
+    return os.path.join(curves_dir, stem + ".npz")
 
 
 def read_wave(input_root, input_path, channel=0):
@@ -120,14 +138,16 @@ class Segmenter(classify.Classifier):
     """A trained ABCD checkpoint opened for segmentation."""
 
     def segment_recording(self, frames, max_length, min_length=1, log_weight=None, gap=None, seg_bonus=0.0,
-                          speaker=None):
+                          speaker=None, posteriors=False, temperature=1.0):
         """``segmentation.segment_frames`` of one recording's frames under the
         categories' prototypes (of ``speaker`` when the decoder embeds speakers)."""
         if self.decoder.embed_speaker is not None and speaker is None:
             raise ValueError("this decoder embeds speakers: a speaker index is required")
         protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(max_length))
+        extra = dict(posteriors=True, temperature=temperature) if posteriors else {}
         return segmentation.segment_frames(self.decoder, protos, frames.to(self.device), max_length,
-                                           min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus)
+                                           min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus,
+                                           **extra)
 
 
 def get_parameters(argv=None):
@@ -159,7 +179,24 @@ def get_parameters(argv=None):
     p.add_argument("--gap_model_out", type=str, default=None, help="where --fit_gap writes the npz")
     p.add_argument("--speaker", type=int, default=None,
                    help="speaker index; required when the decoder embeds speakers")
+    p.add_argument("--posteriors", action="store_true",
+                   help="also sum over every segmentation: append onset_posterior, offset_posterior and "
+                        "span_posterior (how far to trust each cut) after segment_score")
+    p.add_argument("--posterior_temperature", type=float, default=1.0,
+                   help="divides the span scores, the gap scores and the bonus before the posteriors are formed; "
+                        "above 1 softens them (the raw ones are almost all 0 or 1)")
+    p.add_argument("--curves_dir", type=str, default=None,
+                   help="with --posteriors: one npz per recording with the per-frame onset, end and gap posteriors, "
+                        "log_evidence, fs and hop")
+    p.add_argument("--recordings_out", type=str, default=None,
+                   help="with --posteriors: csv with input_path, n_frames, n_segments, path_score, log_evidence, "
+                        "expected_segments per recording")
     a = p.parse_args(argv)
+    if not a.posterior_temperature > 0:
+        p.error("--posterior_temperature must be positive")
+    if not a.posteriors and (a.posterior_temperature != 1.0 or a.curves_dir is not None
+                             or a.recordings_out is not None):
+        p.error("--posterior_temperature, --curves_dir and --recordings_out need --posteriors")
     if a.max_length < 1 or a.max_length > 16383:
         p.error("--max_length must lie in 1 .. 16383")
     if a.min_length < 1 or a.min_length > a.max_length:
@@ -175,9 +212,11 @@ def get_parameters(argv=None):
 def main(argv=None):
     a = get_parameters(argv)
     save_path = a.save_path or os.path.join(a.input_root, "segmented.csv")
-    for path in (save_path, a.gap_model_out):
+    for path in (save_path, a.gap_model_out, a.recordings_out):
         if path and os.path.dirname(path):
             os.makedirs(os.path.dirname(path), exist_ok=True)
+    if a.curves_dir:
+        os.makedirs(a.curves_dir, exist_ok=True)
     table = pd.read_csv(a.recording_table, sep=a.annotation_sep)
     if "input_path" not in table.columns:
         raise SystemExit(f"{a.recording_table}: no input_path column")
@@ -212,7 +251,7 @@ def main(argv=None):
             gap_model = (torch.from_numpy(z["mu"]), torch.from_numpy(z["log_var"]))
 
     lw = seg.log_weight(a.prior, len(table) if a.entire_data_size is None else a.entire_data_size)
-    rows = []
+    rows, recordings, curves = [], [], {}
     for path in paths:
         fs, frame, hop, total, frames = featurise(path)
         d_min = max(a.min_length, min_loadable_length(frame, hop, centering))
@@ -227,7 +266,8 @@ def main(argv=None):
         elif gap_model is not None:
             gap = segmentation.gap_scores(frames, *gap_model)
         out = seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
-                                    seg_bonus=a.segment_bonus, speaker=a.speaker)
+                                    seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
+                                    temperature=a.posterior_temperature)
         if not bool(out["path_score"] > float("-inf")):
             print(f"{path}: no cover of its {frames.shape[0]} frames by segments of {d_min} .. {a.max_length} "
                   "frames (give a gap score or model)", file=sys.stderr)
@@ -237,9 +277,19 @@ def main(argv=None):
         data_type = first["data_type"] if "data_type" in table.columns else "segmented"
         rows += segment_rows(path, out["onset"].tolist(), out["length"].tolist(), out["category"].tolist(),
                              out["score"].tolist(), fs, frame, hop, centering, total, data_type=data_type,
-                             speaker=speaker)
+                             speaker=speaker,
+                             posteriors=[out[c].tolist() for c in POSTERIOR_COLUMNS] if a.posteriors else None)
+        if a.posteriors:
+            recordings.append({"input_path": path, "n_frames": int(frames.shape[0]), "n_segments": len(out["onset"]),
+                               "path_score": float(out["path_score"]), "log_evidence": float(out["log_evidence"]),
+                               "expected_segments": float(out["expected_segments"])})
+            if a.curves_dir:
+                on, end, gp = out["curves"].cpu().numpy()
+                curves[curve_path(a.curves_dir, path)] = dict(onset=on, end=end, gap=gp,
+                                                              log_evidence=float(out["log_evidence"]), fs=fs, hop=hop)
     _native.op_status.sync("segment")
-    write_segments(save_path, rows)
+    write_segments(save_path, rows, posteriors=a.posteriors, recordings_out=a.recordings_out, recordings=recordings,
+                   curves=curves)
     return save_path
 
 
