@@ -690,6 +690,88 @@ int abcd_span_posterior(const double* span, long ld_span, long N, int D, int d_m
                         long ld_post, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Syntax-aware segmentation: category transitions inside the span programme
+ * (DESIGN.md s3.13).  S is that of abcd_span_scores; K categories = the P
+ * prototypes.
+ *
+ * abcd_span_table: the pass of abcd_span_scores keeping every prototype,
+ *   table[(e D + d - 1) ld_k + p] = S[e-d, p, d],  0 <= e <= N, 1 <= d <= D, p < P
+ * (end-major, ld_k >= P; columns P .. ld_k - 1 are not written).  A p that
+ * abcd_span_scores would exclude (S NaN or -inf) and every entry with d > e (row
+ * 0 among them) hold -inf.  Each thread of the emission tile stores its own
+ * four values: no thread reads what another wrote, nothing is folded across
+ * prototype tiles, no atomics, no device-global word, two calls agree bit for
+ * bit.  span_score and span_cat (row stride ld_span >= D) may both be NULL;
+ * given, they come out of the same pass and hold the bits abcd_span_scores
+ * writes; one of them alone is ABCD_EINVAL.  table.max over p and its lowest
+ * argmax are those bits too.  Rows >= N of x, steps >= D, prototypes >= P and
+ * columns >= F are never read.  The workspace holds O (D P doubles).
+ * Limits: those of abcd_span_scores and (N + 1) D ld_k < 2^31; the workspace
+ * query returns 0 beyond them (and for ld_k < P).  ABCD_EINVAL (before any
+ * launch, nothing is written): as abcd_span_scores with table in span_score's
+ * place, ld_k < P, ld_span < D with span_score given.  N = 0 writes row 0 only.
+ * The table takes 8 (N + 1) D ld_k bytes.
+ *
+ * abcd_span_chain_viterbi: the semi-Markov programme with a first-order chain
+ * over the categories of consecutive segments, one recording per launch, in
+ * fp64 with every addition as written (fp32 inputs widened first):
+ *   G[0] = 0,  G[n] = G[n-1] + gap[n-1]         (gap NULL: -inf for n >= 1)
+ *   W[0][k] = -inf
+ *   U[n][k]  = max(G[n] + log_init[k], max_k' (W[n][k'] + log_trans[k' ld_trans + k]))
+ *   Vs[n][k] = max_{d_min <= d <= min(D,n)} (U[n-d][k] + table[(n D + d - 1) ld_k + k]) + seg_bonus
+ *   W[n][k]  = max(W[n-1][k] + gap[n-1], Vs[n][k])
+ *   path_score = max(G[N], max_k W[N][k])
+ * Gap frames are transparent: the transition is paid between consecutive
+ * segments however many gap frames lie between them.  log_trans (K rows,
+ * ld_trans >= K) and log_init are log-probabilities as in abcd_chain_posterior:
+ * -inf is a structural zero, NaN counts as -inf.  NaN and -inf candidates are
+ * excluded; +inf in the table is outside the contract.  Ties: the smallest d
+ * in Vs; the gap against a segment in W; the initial term against any
+ * predecessor in U, then the lowest k'; at the end "no segment", then the
+ * lowest k.  The backtrack from (N, k) follows d = 0 to (n-1, k), otherwise
+ * emits (n-d, d, k) and goes to (n-d, the k' chosen in U[n-d][k]), and stops at
+ * the initial term.  Segments come out in time order, N / d_min entries per
+ * buffer, n_segments valid: seg_score is the chosen table entry, seg_link the
+ * log_init or log_trans term paid on entering the segment, widened to fp64.
+ * An uncoverable recording gives path_score = -inf and n_segments = 0.  W_out
+ * ((N + 1) x K doubles) may be NULL.  One workgroup (1024 threads up to K =
+ * 256, 256 threads above) runs the whole loop and the backtrack; lanes run
+ * over k, the waves split d and k' and their partial maxima are combined in
+ * wave order under the tie rules, so nothing is decided by scheduling and two
+ * calls agree bit for bit.
+ * log_trans is resident in LDS up to K = 128 and streamed from global memory
+ * above (abcd_span_chain_plan says which, with the launch width and the LDS
+ * bytes; it is a pure function).  The workspace holds U ((N + 1) K doubles)
+ * and the two back-pointer planes ((N + 1) K int32 each).
+ * Limits: 1 <= K <= 1024, those of abcd_span_table with ld_k; the workspace
+ * query returns 0 beyond them ((N + 1) D K >= 2^31 included).  ABCD_EINVAL
+ * (decided on the host before any launch, nothing is written): those limits,
+ * d_min outside 1 .. D, ld_k < K, ld_trans < K, a NULL among table, log_trans,
+ * log_init, path_score, n_segments and the five segment buffers while N > 0, a
+ * missing or short workspace.  N = 0 gives path_score = 0, n_segments = 0 and
+ * W_out[0][k] = -inf (each where not NULL) and reads nothing.
+ *
+ * Measured on one MI355X at N = 15 000, D = 200, K = 128, F = 129 (DESIGN.md
+ * s3.13): abcd_span_table 9.7 ms (0.96 x abcd_span_scores),
+ * abcd_span_chain_viterbi 209 ms (14 us per step; 19 us at K = 130, streaming):
+ * the step is bound by reading its 205 KB table row on one CU.
+ *
+ * No timing or dispatch id is assigned to these entry points.
+ * ---------------------------------------------------------------------- */
+size_t abcd_span_table_workspace_bytes(long N, int D, int P, long ld_k);
+int abcd_span_table(const float* x, long ld_x, long N, int F, int P, int D, int T_proto, const float* proto_mu,
+                    long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                    const float* log_weight, double* table, long ld_k, double* span_score, int32_t* span_cat,
+                    long ld_span, void* ws, size_t ws_bytes, void* stream);
+int abcd_span_chain_plan(int K, int D, int* resident, int* threads, size_t* lds_bytes);
+size_t abcd_span_chain_workspace_bytes(long N, int D, int K);
+int abcd_span_chain_viterbi(const double* table, long ld_k, long N, int D, int K, int d_min, const float* gap,
+                            double seg_bonus, const float* log_trans, long ld_trans, const float* log_init,
+                            double* path_score, int32_t* n_segments, int32_t* seg_onset, int32_t* seg_length,
+                            int32_t* seg_cat, double* seg_score, double* seg_link, double* W_out, void* ws,
+                            size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Time-warped scoring: a segment aligned to a prototype.  abcd_pairwise_nll
  * scores frame t against step t; here the T_proto steps of prototype p are the
  * states of a left-to-right HMM and frame t of segment b is emitted by state

@@ -13,11 +13,15 @@
 //                 prototype per (s, d) folded into the end-major output
 //   span_viterbi  one workgroup: the semi-Markov dynamic programme over the
 //                 output of span_nll and the backtrack
-//   span_nll<true>  the same pass with the log-sum over the prototypes beside
+//   span_nll<SPAN_LSE>  the same pass with the log-sum over the prototypes beside
 //                 (or instead of) the maximum (abcd_span_evidence, s3.12)
 //   span_fb       one workgroup: the sum form of span_viterbi, forward and
 //                 backward over one recording, and the per-frame posteriors
 //   span_post_table  the per-span posteriors from the lattice, many workgroups
+//   span_nll<SPAN_TABLE>  the same pass keeping every prototype's score
+//                 (abcd_span_table, s3.13)
+//   span_chain    one workgroup: span_viterbi with a first-order chain over the
+//                 categories of consecutive segments, state (frame, last category)
 //
 // span_nll runs on the emission tile pair_nll runs on (abcd_emtile.h: the
 // staging, the per-term expressions and the order of a frame's sums, F columns
@@ -98,13 +102,24 @@ DEV double logaddexp_d(double a, double b) {
 // sum for the first prototype tile and folds later tiles into what it wrote
 // with a logaddexp.  The maximum's code is the same statements in both
 // instantiations, span_score / span_cat may be NULL in this one.
-template <bool LSE>
+//
+// MODE = SPAN_TABLE (abcd_span_table, s3.13) keeps the per-prototype scores
+// instead: after a step's last chunk every thread stores its own four S values
+// (two starts x two prototypes, an excluded one as -inf) at table[(e D + t) ldk
+// + p], table passed in span_lse's place.  No thread reads what another wrote
+// and nothing is folded across the prototype tiles; the 16-lane reduction runs
+// only when span_score / span_cat are asked for, with the statements of the
+// other two instantiations.
+constexpr int SPAN_MAX = 0, SPAN_LSE = 1, SPAN_TABLE = 2;
+
+template <int MODE>
 __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, long ldx, long N, int F, int P, int D,
                                                 const float* __restrict__ MU, long ldm,
                                                 const float* __restrict__ LV, long ldl,
                                                 const double* __restrict__ Otab, const float* __restrict__ LW,
                                                 double* __restrict__ span_score, int32_t* __restrict__ span_cat,
-                                                double* __restrict__ span_lse, long lds) {
+                                                double* __restrict__ span_lse, long lds, long ldk) {
+  constexpr bool LSE = MODE == SPAN_LSE, TAB = MODE == SPAN_TABLE;
   __shared__ EmTile tile;
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const long s0 = (long)blockIdx.x * EM_TR;
@@ -154,6 +169,14 @@ __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, lon
           if (!(sa > -INFINITY)) { sa = -INFINITY; arg = INT_MAX; }  // NaN and -inf: excluded
           if (!(sb > -INFINITY)) { sb = -INFINITY; ab = INT_MAX; }
           const double ua = sa, ub = sb;
+          if (TAB) {
+            if (v) {
+              double* const row = span_lse + (e * D + t) * ldk;
+              if (pa < P) row[pa] = ua;
+              if (pb < P) row[pb] = ub;
+            }
+            if (!span_score) continue;  // uniform: the whole workgroup skips the reduction
+          }
           if (sb > sa) { sa = sb; arg = ab; }
           wave_argmax<16>(sa, arg);  // the 16 lanes of one start
           if (LSE) {
@@ -539,8 +562,195 @@ __global__ __launch_bounds__(256) void span_post_table(const double* __restrict_
   span_post[e * ldp + d - 1] = v > 0.0 ? v : 0.0;
 }
 
+// the table entries with d > e (row 0 among them), prototypes < P: -inf
+__global__ __launch_bounds__(256) void span_table_fill(long rows, int D, int P, double* __restrict__ table, long ldk) {
+  const long at = (long)blockIdx.x * 256 + threadIdx.x;
+  if (at >= rows * D * P) return;
+  const long ec = at / P;
+  const int p = (int)(at - ec * P);
+  const long e = ec / D;
+  const int c = (int)(ec - e * D);  // d - 1
+  if (c < e) return;
+  table[ec * ldk + p] = -INFINITY;
+}
+
+// span_viterbi with category transitions: one workgroup, one
+// launch, the state is (frame, last category).
+//   G[n]     = G[n-1] + gap[n-1]                                  no segment yet
+//   U[n][k]  = max(G[n] + log_init[k], max_k' (W[n][k'] + log_trans[k'][k]))
+//   Vs[n][k] = max_{d_min <= d <= min(D, n)} (U[n-d][k] + T[n,d,k]) + bonus
+//   W[n][k]  = max(W[n-1][k] + gap[n-1], Vs[n][k])
+// Lanes run over k in both maxima, so a table row T[n,d,:], a lattice row
+// U[n-d,:] and a matrix row log_trans[k',:] are read contiguously; the waves
+// (16 up to K = SC_WIDE_K, 4 above: the partial results must fit LDS) split d
+// (phase A) and k' (phase B), each thread taking its candidates in ascending
+// order under a strict comparison, and the waves' partial results of a k meet
+// in LDS and are combined in wave order with the tie rule spelled out (the
+// smaller d, the lower k'), so no comparison is decided by scheduling.  The
+// step is latency: 16 waves keep 16 rows of the table in flight at once.
+// The gap wins a tie in W, the initial term in U.  NaN and -inf candidates fail
+// every comparison.  U and the two back-pointer planes (d, 0 for the gap; k',
+// -1 for the initial term) live in the workspace: the workgroup reads its own
+// global stores a barrier later.  W[n] and log_init stay in LDS; RES keeps
+// log_trans there too (K <= SC_RES_K), otherwise its rows stream from global
+// memory.  U[N] is not formed: no segment starts at N.
+constexpr int SC_THREADS = 1024;  // the widest launch
+constexpr int SC_WIDE_K = 256;    // 16 waves up to here, 4 above
+constexpr int SC_RES_K = 128;   // log_trans resident in LDS (64 KB) up to here
+constexpr int SC_MAX_K = 1024;
+
+static int span_chain_waves(int K) { return K <= SC_WIDE_K ? SC_THREADS / 64 : 4; }
+
+static size_t span_chain_lds(int K) {
+  const int nw = span_chain_waves(K);
+  return (size_t)K * ((2 + nw) * sizeof(double) + nw * sizeof(int)) +
+         (K <= SC_RES_K ? (size_t)K * K * sizeof(float) : 0);
+}
+
+template <bool RES>
+__global__ __launch_bounds__(SC_THREADS) void span_chain(
+    const double* __restrict__ T, long ldk, long N, int D, int K, int dmin, const float* __restrict__ gap, double bonus,
+    const float* __restrict__ LT, long ldt, const float* __restrict__ LI, double* __restrict__ path_score,
+    int32_t* __restrict__ n_segments, int32_t* __restrict__ seg_onset, int32_t* __restrict__ seg_length,
+    int32_t* __restrict__ seg_cat, double* __restrict__ seg_score, double* __restrict__ seg_link,
+    double* __restrict__ W_out, double* U, int32_t* back_d, int32_t* back_k) {
+  extern __shared__ __attribute__((aligned(16))) double sc_lds[];
+  double* const Wc = sc_lds;                        // W[n][k]
+  double* const Li = Wc + K;                        // log_init, widened
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nt = blockDim.x, nw = nt >> 6;
+  double* const pv = Li + K;                        // the waves' partial maxima, nw x K
+  int* const pa = (int*)(pv + nw * K);              // and their arguments
+  const float* const lt = (const float*)(pa + nw * K);  // RES: K x K
+  for (int k = tid; k < K; k += nt) {
+    const double li = (double)LI[k];
+    Wc[k] = -INFINITY;
+    Li[k] = li;
+    U[k] = li;  // G[0] = 0 and W[0] = -inf: the initial term
+    back_k[k] = -1;
+    if (W_out) W_out[k] = -INFINITY;
+  }
+  if (RES) {
+    float* const dst = (float*)(pa + nw * K);
+    for (int i = tid; i < K * K; i += nt) dst[i] = LT[(long)(i / K) * ldt + i % K];
+  }
+  __syncthreads();
+  double G = 0.0;
+  for (long n = 1; n <= N; ++n) {
+    const double gv = gap ? (double)gap[n - 1] : -INFINITY;
+    G = G + gv;
+    // ---- phase A: the best segment of each k that ends at n
+    const int dmax = (int)min((long)D, n);
+    for (int k = lane; k < K; k += 64) {
+      double best = -INFINITY;
+      int bd = INT_MAX;
+      const double* const Trow = T + (n * D - 1) * ldk + k;  // + d ldk
+      const double* const Urow = U + n * K + k;               // - d K
+#pragma unroll 4
+      for (int d = dmin + w; d <= dmax; d += nw) {
+        const double c = Urow[-(long)d * K] + Trow[(long)d * ldk];
+        if (c > best) { best = c; bd = d; }
+      }
+      pv[w * K + k] = best;
+      pa[w * K + k] = bd;
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nt) {
+      double best = pv[k];
+      int bd = pa[k];
+      for (int i = 1; i < nw; ++i) {
+        const double b2 = pv[i * K + k];
+        const int d2 = pa[i * K + k];
+        if (b2 > best || (b2 == best && d2 < bd)) { best = b2; bd = d2; }
+      }
+      const double seg = best + bonus, gapc = Wc[k] + gv;
+      const bool vg = gapc > -INFINITY, vs = seg > -INFINITY && bd != INT_MAX;
+      double Wn = -INFINITY;
+      int choice = 0;  // 0: the gap (or nothing); d: a segment of k of d frames ends here
+      if (vg && (!vs || gapc >= seg)) Wn = gapc;
+      else if (vs) { Wn = seg; choice = bd; }
+      Wc[k] = Wn;
+      back_d[n * K + k] = choice;
+      if (W_out) W_out[n * K + k] = Wn;
+    }
+    __syncthreads();
+    if (n == N) break;
+    // ---- phase B: the best way into a segment of k that starts at n
+    for (int k = lane; k < K; k += 64) {
+      double best = -INFINITY;
+      int bk = INT_MAX;
+#pragma unroll 4
+      for (int kp = w; kp < K; kp += nw) {
+        const double c = Wc[kp] + (double)(RES ? lt[kp * K + k] : LT[(long)kp * ldt + k]);
+        if (c > best) { best = c; bk = kp; }
+      }
+      pv[w * K + k] = best;
+      pa[w * K + k] = bk;
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nt) {
+      double best = pv[k];
+      int bk = pa[k];
+      for (int i = 1; i < nw; ++i) {
+        const double b2 = pv[i * K + k];
+        const int k2 = pa[i * K + k];
+        if (b2 > best || (b2 == best && k2 < bk)) { best = b2; bk = k2; }
+      }
+      const double init = G + Li[k];
+      const bool vi = init > -INFINITY, vp = best > -INFINITY && bk != INT_MAX;
+      double Un = -INFINITY;
+      int from = -1;  // -1: the initial term (or nothing)
+      if (vi && (!vp || init >= best)) Un = init;
+      else if (vp) { Un = best; from = bk; }
+      U[n * K + k] = Un;
+      back_k[n * K + k] = from;
+    }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  double best = G > -INFINITY ? G : -INFINITY;  // "no segment" wins a tie, then the lowest k
+  int kb = -1;
+  for (int k = 0; k < K; ++k)
+    if (Wc[k] > best) { best = Wc[k]; kb = k; }
+  *path_score = best;
+  int count = 0;
+  {
+    long n = N;
+    int k = kb;
+    while (k >= 0 && n > 0) {
+      const int d = back_d[n * K + k];
+      if (d == 0) { --n; continue; }
+      ++count;
+      n -= d;
+      k = back_k[n * K + k];
+    }
+  }
+  *n_segments = count;
+  int i = count;
+  long n = N;
+  int k = kb;
+  while (k >= 0 && n > 0) {
+    const int d = back_d[n * K + k];
+    if (d == 0) { --n; continue; }
+    --i;
+    seg_onset[i] = (int32_t)(n - d);
+    seg_length[i] = d;
+    seg_cat[i] = k;
+    seg_score[i] = T[(n * D + d - 1) * ldk + k];
+    n -= d;
+    const int from = back_k[n * K + k];
+    seg_link[i] = from < 0 ? Li[k] : (double)LT[(long)from * ldt + k];
+    k = from;
+  }
+}
+
 static bool span_shape_ok(long N, int D) {
   return D >= 1 && D <= SP_MAX_D && N >= 0 && N < (1L << 31) && (N + 1) * (long)D < (1L << 31);
+}
+
+// the per-category table's index limit on top of span_shape_ok
+static bool span_table_ok(long N, int D, long ldk) {
+  return span_shape_ok(N, D) && ldk >= 1 && ldk < (1L << 31) && (N + 1) * (long)D * ldk < (1L << 31);
 }
 
 }  // namespace abcd
@@ -569,8 +779,8 @@ extern "C" int abcd_span_scores(const float* x, long ld_x, long N, int F, int P,
   if (N == 0) return 0;
   double* Otab = (double*)ws;
   span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<false><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
-                                                 log_weight, span_score, span_cat, nullptr, ld_span);
+  span_nll<SPAN_MAX><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+                                                    log_weight, span_score, span_cat, nullptr, ld_span, 0);
   ABCD_CHECK_LAUNCH();
   return 0;
 }
@@ -598,8 +808,8 @@ extern "C" int abcd_span_evidence(const float* x, long ld_x, long N, int F, int 
   if (N == 0) return 0;
   double* Otab = (double*)ws;
   span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<true><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
-                                                log_weight, span_score, span_cat, span_lse, ld_span);
+  span_nll<SPAN_LSE><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+                                                    log_weight, span_score, span_cat, span_lse, ld_span, 0);
   ABCD_CHECK_LAUNCH();
   return 0;
 }
@@ -674,5 +884,101 @@ extern "C" int abcd_span_posterior(const double* span, long ld_span, long N, int
                                                            ld_post);
     ABCD_CHECK_LAUNCH();
   }
+  return 0;
+}
+
+extern "C" size_t abcd_span_table_workspace_bytes(long N, int D, int P, long ld_k) {
+  if (!span_table_ok(N, D, ld_k) || P < 1 || ld_k < P) return 0;
+  return abcd_span_scores_workspace_bytes(N, D, P);  // O[p, d]
+}
+
+extern "C" int abcd_span_table(const float* x, long ld_x, long N, int F, int P, int D, int T_proto,
+                               const float* proto_mu, long ld_mu, const float* proto_lv, long ld_lv,
+                               const float* proto_offset_logits, const float* log_weight, double* table, long ld_k,
+                               double* span_score, int32_t* span_cat, long ld_span, void* ws, size_t ws_bytes,
+                               void* stream) {
+  ABCD_REQUIRE(span_table_ok(N, D, ld_k) && P >= 1 && F >= 1 && T_proto >= D);
+  ABCD_REQUIRE(ld_x >= F && ld_mu >= F && ld_lv >= F && ld_k >= P);
+  ABCD_REQUIRE(!span_score == !span_cat);  // the best outputs come together or not at all
+  ABCD_REQUIRE(!span_score || ld_span >= D);
+  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits && table));
+  const size_t need = abcd_span_table_workspace_bytes(N, D, P, ld_k);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  const long rows = std::min(N, (long)D - 1) + 1;
+  if (table) {
+    span_table_fill<<<cdiv(rows * D * P, 256), 256, 0, s>>>(rows, D, P, table, ld_k);
+    ABCD_CHECK_LAUNCH();
+  }
+  if (span_score) {
+    span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, nullptr, ld_span);
+    ABCD_CHECK_LAUNCH();
+  }
+  if (N == 0) return 0;
+  double* Otab = (double*)ws;
+  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
+  span_nll<SPAN_TABLE><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+                                                      log_weight, span_score, span_cat, table, ld_span, ld_k);
+  ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int abcd_span_chain_plan(int K, int D, int* resident, int* threads, size_t* lds_bytes) {
+  ABCD_REQUIRE(K >= 1 && K <= SC_MAX_K && D >= 1 && D <= SP_MAX_D);
+  if (resident) *resident = K <= SC_RES_K;
+  if (threads) *threads = 64 * span_chain_waves(K);
+  if (lds_bytes) *lds_bytes = span_chain_lds(K);
+  return 0;
+}
+
+extern "C" size_t abcd_span_chain_workspace_bytes(long N, int D, int K) {
+  if (K < 1 || K > SC_MAX_K || !span_table_ok(N, D, K)) return 0;
+  // U, then the two back-pointer planes
+  return ((size_t)N + 1) * (size_t)K * (sizeof(double) + 2 * sizeof(int32_t)) + 256;
+}
+
+extern "C" int abcd_span_chain_viterbi(const double* table, long ld_k, long N, int D, int K, int d_min,
+                                       const float* gap, double seg_bonus, const float* log_trans, long ld_trans,
+                                       const float* log_init, double* path_score, int32_t* n_segments,
+                                       int32_t* seg_onset, int32_t* seg_length, int32_t* seg_cat, double* seg_score,
+                                       double* seg_link, double* W_out, void* ws, size_t ws_bytes, void* stream) {
+  ABCD_REQUIRE(K >= 1 && K <= SC_MAX_K && span_table_ok(N, D, ld_k) && d_min >= 1 && d_min <= D);
+  ABCD_REQUIRE(ld_k >= K && ld_trans >= K);
+  ABCD_REQUIRE(N == 0 || (table && log_trans && log_init && path_score && n_segments && seg_onset && seg_length &&
+                          seg_cat && seg_score && seg_link));
+  const size_t need = abcd_span_chain_workspace_bytes(N, D, K);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) {  // the empty path: score 0, no segments, W[0] = -inf, nothing is read
+    if (path_score) ABCD_TRY(hipMemsetAsync(path_score, 0, sizeof(double), s));
+    if (n_segments) ABCD_TRY(hipMemsetAsync(n_segments, 0, sizeof(int32_t), s));
+    if (W_out) {
+      span_table_fill<<<cdiv(K, 256), 256, 0, s>>>(1, 1, K, W_out, K);
+      ABCD_CHECK_LAUNCH();
+    }
+    return 0;
+  }
+  static bool attr = false;
+  if (!attr) {
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)span_chain_lds(SC_RES_K)));
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)std::max(span_chain_lds(SC_WIDE_K), span_chain_lds(SC_MAX_K))));
+    attr = true;
+  }
+  double* U = (double*)ws;
+  int32_t* back_d = (int32_t*)(U + (N + 1) * K);
+  int32_t* back_k = back_d + (N + 1) * K;
+  if (K <= SC_RES_K)
+    span_chain<true><<<1, 64 * span_chain_waves(K), span_chain_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, seg_bonus, log_trans,
+                                                              ld_trans, log_init, path_score, n_segments, seg_onset,
+                                                              seg_length, seg_cat, seg_score, seg_link, W_out, U,
+                                                              back_d, back_k);
+  else
+    span_chain<false><<<1, 64 * span_chain_waves(K), span_chain_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, seg_bonus, log_trans,
+                                                               ld_trans, log_init, path_score, n_segments, seg_onset,
+                                                               seg_length, seg_cat, seg_score, seg_link, W_out, U,
+                                                               back_d, back_k);
+  ABCD_CHECK_LAUNCH();
   return 0;
 }

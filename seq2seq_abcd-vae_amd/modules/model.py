@@ -970,6 +970,32 @@ class RNN_Variational_Decoder(torch.nn.Module):
                                                 offl.reshape(-1), log_weight, P, D, bool(want_best))
         return (lse, score, cat) if want_best else (lse, None, None)
 
+    def span_table(self, prototypes, frames, max_length, log_weight=None, want_best=False):
+        """``span_scores`` keeping every category: ``(table, span_score,
+        span_cat)`` with ``table[e, d - 1, p]`` (float64, ``N + 1 x max_length
+        x P``, end-major) the ``log_weight[p] - em - off`` of frames ``e - d ..
+        e - 1`` as one segment of prototype p; excluded prototypes and entries
+        with ``d > e`` hold -inf.  This is what the dynamic programme with
+        category transitions reads (``ops.span_chain_viterbi``); it takes ``8
+        (N + 1) max_length P`` bytes.  With ``want_best`` the same pass also
+        returns ``span_scores``' two tables, bit for bit; without it they are
+        None.  Forward-only, under ``torch.no_grad()``."""
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(frames)
+        F, D = self.rnn_cell.cell.input_size, int(max_length)
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= D >= 1):
+            raise ValueError(f"span_table: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
+        if frames.dim() != 2 or frames.shape[1] != F:
+            raise ValueError(f"span_table: frames must be N x {F}, got {tuple(frames.shape)}")
+        P = int(offl.shape[1])
+        with torch.no_grad():
+            table, score, cat = ops.span_table(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F),
+                                               offl.reshape(-1), log_weight, P, D, bool(want_best))
+        return (table, score, cat) if want_best else (table, None, None)
+
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()
         return torch.tensor([int((lengths > t).sum()) for t in range(int(lengths.max()))], dtype=torch.int64)

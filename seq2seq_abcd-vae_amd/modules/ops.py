@@ -33,9 +33,11 @@ operator                   replaces (reference)                            C ent
 ``abcd::warp_path``        (none: the best alignment and its costs)        ``abcd_warp_path``
 ``abcd::span_evidence``    (none: span scores summed over the categories)  ``abcd_span_evidence``
 ``abcd::span_posterior``   (none: posteriors over all covers by segments)  ``abcd_span_posterior``
+``abcd::span_table``       (none: span scores of every category)           ``abcd_span_table``
+``abcd::span_chain_viterbi`` (none: the best cover under a category chain) ``abcd_span_chain_viterbi``
 =========================  ==============================================  =========================================
 
-The last twelve are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
+The last fourteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -1068,6 +1070,133 @@ def _(span, d_min, gap, seg_bonus, want_table):
 _forward_only(span_posterior, "span_posterior")
 
 
+_TABLE_LIMIT = "D > 16383, (N + 1) * D >= 2^31 or the table's index limit (N + 1) * D * K >= 2^31"
+
+
+@torch.library.custom_op("abcd::span_table", mutates_args=())
+def span_table(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_logits: Tensor,
+               log_weight: Optional[Tensor], P: int, D: int, want_best: bool) -> List[Tensor]:
+    """-> [table (N + 1 x D x P, fp64), span_score, span_cat]: span_scores' pass
+    keeping every prototype, table[e, d - 1, p] = log_weight[p] - em - off of
+    frames e - d .. e - 1 as one segment of prototype p that ends after d
+    frames (abcd_span_table); excluded prototypes and entries with d > e hold
+    -inf.  With want_best the same pass also gives span_scores' two tables, bit
+    for bit; without it they are 0 x 0."""
+    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
+        N.require_gpu(t)
+    P, D = int(P), int(D)
+    if frames.dim() != 2 or frames.shape[1] < 1:
+        raise ValueError(f"span_table: frames must be N x F, got {tuple(frames.shape)}")
+    n, F = (int(v) for v in frames.shape)
+    if P < 1 or D < 1:
+        raise ValueError("span_table: P and D must be at least 1")
+    dev = frames.device
+    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
+    ol = proto_offset_logits.float().contiguous()
+    rows = int(ol.numel())
+    if rows % P or rows // P < D:
+        raise ValueError(f"span_table: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
+                         f"got {rows}")
+    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
+        raise ValueError(f"span_table: proto_mu and proto_lv must be {(rows, F)}")
+    lw = None
+    if log_weight is not None:
+        N.require_gpu(log_weight)
+        if log_weight.numel() != P:
+            raise ValueError(f"span_table: log_weight must hold {P} entries, got {log_weight.numel()}")
+        lw = log_weight.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_span_table_workspace_bytes(n, D, P, P)
+    if nbytes == 0:
+        raise N.HipError(f"span_table: unsupported shape ({_TABLE_LIMIT}); N = {n}, D = {D}, K = {P}")
+    ws = N.workspace(nbytes, dev)
+    table = torch.empty(n + 1, D, P, dtype=torch.float64, device=dev)
+    shape = (n + 1, D) if want_best else (0, 0)
+    score = torch.empty(shape, dtype=torch.float64, device=dev)
+    cat = torch.empty(shape, dtype=torch.int32, device=dev)
+    N.check(L_.abcd_span_table(N.ptr(x), ldx, n, F, P, D, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                               N.ptr(lw), N.ptr(table), P, N.ptr(score) if want_best else None,
+                               N.ptr(cat) if want_best else None, D, N.ptr(ws), ws.numel(), N.stream()),
+            "span table")
+    return [table, score, cat]
+
+
+@span_table.register_fake
+def _(frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D, want_best):
+    n = frames.shape[0]
+    shape = (n + 1, int(D)) if want_best else (0, 0)
+    return [frames.new_empty(n + 1, int(D), int(P), dtype=torch.float64),
+            frames.new_empty(shape, dtype=torch.float64), frames.new_empty(shape, dtype=torch.int32)]
+
+
+_forward_only(span_table, "span_table")
+
+
+@torch.library.custom_op("abcd::span_chain_viterbi", mutates_args=())
+def span_chain_viterbi(table: Tensor, d_min: int, gap: Optional[Tensor], seg_bonus: float, log_trans: Tensor,
+                       log_init: Tensor, want_w: bool) -> List[Tensor]:
+    """-> [path_score (0-d, fp64), n_segments (0-d, int32), onset, length,
+    category (N // d_min each, int32), score, link (N // d_min, fp64), W ((N +
+    1) x K fp64, or empty)]: the best cover of the N frames by segments of
+    d_min .. D frames and gap frames under span_table's table (N + 1 x D x K)
+    with the transition log_trans[k', k] (K x K, row-strided views pass without
+    a copy) paid between consecutive segments and log_init[k] on the first
+    (abcd_span_chain_viterbi).  link is that term per segment.  Only the first
+    n_segments entries of the segment lists are written."""
+    for t in (table, log_trans, log_init):
+        N.require_gpu(t)
+    if table.dim() != 3 or min(table.shape) < 1:
+        raise ValueError(f"span_chain_viterbi: table must be N + 1 x D x K, got {tuple(table.shape)}")
+    n, D, K = int(table.shape[0]) - 1, int(table.shape[1]), int(table.shape[2])
+    d_min = int(d_min)
+    if d_min < 1 or d_min > D:
+        raise ValueError(f"span_chain_viterbi: d_min must lie in 1 .. {D}, got {d_min}")
+    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
+        raise ValueError(f"span_chain_viterbi: log_trans must be {K} x {K} and log_init hold {K} entries, got "
+                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
+    if K > 1024:
+        raise ValueError(f"span_chain_viterbi: at most 1024 categories, got {K}")
+    dev = table.device
+    tb = table.double().contiguous()
+    lt, ldt = _rows(log_trans.float())
+    li = log_init.float().contiguous()
+    g = None
+    if gap is not None:
+        N.require_gpu(gap)
+        if gap.numel() != n:
+            raise ValueError(f"span_chain_viterbi: gap must hold {n} entries, got {gap.numel()}")
+        g = gap.float().contiguous()
+    L_ = N.lib()
+    nbytes = L_.abcd_span_chain_workspace_bytes(n, D, K)
+    if nbytes == 0:
+        raise N.HipError(f"span_chain_viterbi: unsupported shape ({_TABLE_LIMIT}); N = {n}, D = {D}, K = {K}")
+    ws = N.workspace(nbytes, dev)
+    cap = n // d_min
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    ps, ns = torch.empty((), **f64), torch.empty((), **i32)
+    onset, length, cat = (torch.zeros(max(cap, 1), **i32) for _ in range(3))
+    score, link = torch.zeros(max(cap, 1), **f64), torch.zeros(max(cap, 1), **f64)
+    W = torch.empty((n + 1, K) if want_w else (0, K), **f64)
+    N.check(L_.abcd_span_chain_viterbi(N.ptr(tb), K, n, D, K, d_min, N.ptr(g), float(seg_bonus), N.ptr(lt), ldt,
+                                       N.ptr(li), N.ptr(ps), N.ptr(ns), N.ptr(onset), N.ptr(length), N.ptr(cat),
+                                       N.ptr(score), N.ptr(link), N.ptr(W) if want_w else None, N.ptr(ws),
+                                       ws.numel(), N.stream()), "span chain viterbi")
+    return [ps, ns, onset[:cap], length[:cap], cat[:cap], score[:cap], link[:cap], W]
+
+
+@span_chain_viterbi.register_fake
+def _(table, d_min, gap, seg_bonus, log_trans, log_init, want_w):
+    n, K = table.shape[0] - 1, table.shape[2]
+    cap = n // int(d_min)
+    e = table.new_empty
+    return [e((), dtype=torch.float64), e((), dtype=torch.int32), e(cap, dtype=torch.int32),
+            e(cap, dtype=torch.int32), e(cap, dtype=torch.int32), e(cap, dtype=torch.float64),
+            e(cap, dtype=torch.float64), e((n + 1, K) if want_w else (0, K), dtype=torch.float64)]
+
+
+_forward_only(span_chain_viterbi, "span_chain_viterbi")
+
+
 # ----------------------------------------------------------------------------
 # time-warped scoring: segments aligned to prototypes (forward-only)
 # ----------------------------------------------------------------------------
@@ -1232,7 +1361,7 @@ _forward_only(griffin_lim, "griffin_lim")
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
        "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
-       "warp_nll", "warp_path", "span_evidence", "span_posterior")
+       "warp_nll", "warp_path", "span_evidence", "span_posterior", "span_table", "span_chain_viterbi")
 
 
 def registered() -> Sequence[str]:

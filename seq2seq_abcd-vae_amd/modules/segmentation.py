@@ -11,7 +11,11 @@ moments from the frames an existing annotation leaves uncovered.  Without a
 gap model the segments tile the recording.  ``segment_posteriors`` (and
 ``segment_frames(posteriors=True)``) say how far to trust the cut: onset, end,
 gap and span posteriors over every cover and the recording's log evidence
-(``ops.span_evidence`` / ``ops.span_posterior``)."""
+(``ops.span_evidence`` / ``ops.span_posterior``).
+``segment_frames(transitions=...)`` puts a first-order chain over the
+categories of consecutive segments inside the programme
+(``ops.span_table`` / ``ops.span_chain_viterbi``); ``count_transitions`` and
+``refit_transitions`` fit that chain on uncut recordings by Viterbi training."""
 import math
 
 import torch
@@ -21,7 +25,7 @@ from . import ops
 
 
 def segment_frames(decoder, prototypes, frames, max_length, min_length=1, log_weight=None, gap=None, seg_bonus=0.0,
-                   posteriors=False, temperature=1.0):
+                   posteriors=False, temperature=1.0, transitions=None, include_weight=False):
     """The best segmentation of ``frames`` (N x F on the GPU): a dict of
     ``onset``, ``length``, ``category`` (int64, one entry per segment in time
     order, frames), ``score`` (float64: each segment's ``log_weight[cat] - em -
@@ -41,11 +45,33 @@ def segment_frames(decoder, prototypes, frames, max_length, min_length=1, log_we
     float64 under the posterior over every cover at ``temperature`` (see
     ``segment_posteriors``), and ``log_evidence``, ``expected_segments`` (0-d
     float64) and ``curves`` (3 x (N + 1) float64: the onset, end and gap
-    posteriors per frame)."""
+    posteriors per frame).
+
+    With ``transitions`` (a ``sequence.TransitionModel`` or a ``(log_trans,
+    log_init)`` pair over the K prototypes) the categories of consecutive
+    segments form a first-order chain INSIDE the programme, so the matrix moves
+    boundaries as well as labels: the per-category table
+    (``decoder.span_table``) goes through ``ops.span_chain_viterbi``, the
+    transition being paid between consecutive segments however many gap frames
+    lie between them and ``log_init`` on the first.  The chain is the prior
+    over the categories, so the table is built WITHOUT ``log_weight`` unless
+    ``include_weight`` is set.  ``score`` is then the chosen table entry and
+    the dict additionally holds ``link`` (float64 per segment: the ``log_init``
+    or ``log_trans`` term paid on entering it) and ``context_free_category``
+    (int64: the lowest argmax over k of ``table[e, d, :] + log_weight`` at the
+    chosen span, what the span alone would have been labelled).
+    ``path_score`` sums scores, links, bonuses and gaps.  Together with
+    ``posteriors=True`` this raises ValueError."""
     N.require_gpu(frames)
     n, D, d_min = int(frames.shape[0]), int(max_length), int(min_length)
     if not 1 <= d_min <= D:
         raise ValueError(f"segment_frames: 1 <= min_length <= max_length, got {d_min} and {D}")
+    if transitions is not None:
+        if posteriors:
+            raise ValueError("segment_frames: posteriors under a transition model are not available; give "
+                             "transitions or posteriors=True, not both")
+        return _segment_chain(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions,
+                              include_weight)
     with torch.no_grad():
         if posteriors:
             lse, score, cat = decoder.span_evidence(prototypes, frames, D, log_weight=log_weight, want_best=True)
@@ -63,6 +89,94 @@ def segment_frames(decoder, prototypes, frames, max_length, min_length=1, log_we
                    span_posterior=table[end, out["length"] - 1], log_evidence=log_z, curves=post,
                    expected_segments=post[1].sum())
     return out
+
+
+def _chain_of(transitions, device):
+    """(log_trans K x K, log_init K) fp32 on ``device`` from a TransitionModel or a pair."""
+    if hasattr(transitions, "log_trans") and hasattr(transitions, "log_init"):
+        lt, li = transitions.log_trans, transitions.log_init
+    else:
+        lt, li = transitions
+    lt = torch.as_tensor(lt).to(device=device, dtype=torch.float32)
+    li = torch.as_tensor(li).to(device=device, dtype=torch.float32).reshape(-1)
+    if lt.dim() != 2 or lt.shape[0] != lt.shape[1] or li.numel() != lt.shape[0]:
+        raise ValueError(f"transitions: log_trans must be K x K and log_init hold K entries, got {tuple(lt.shape)} "
+                         f"and {tuple(li.shape)}")
+    return lt, li
+
+
+def _segment_chain(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions, include_weight):
+    """segment_frames under a transition model (see there)."""
+    lt, li = _chain_of(transitions, frames.device)
+    K = int(prototypes[2].shape[1])
+    if lt.shape[0] != K:
+        raise ValueError(f"segment_frames: the transition model has {lt.shape[0]} categories, the prototypes {K}")
+    lw = None if log_weight is None else torch.as_tensor(log_weight, device=frames.device).float().reshape(-1)
+    with torch.no_grad():
+        table, _, _ = decoder.span_table(prototypes, frames, D, log_weight=lw if include_weight else None)
+        g = None if gap is None else torch.as_tensor(gap, device=frames.device).float()
+        ps, ns, onset, length, category, seg, link, _ = ops.span_chain_viterbi(table, d_min, g, float(seg_bonus), lt,
+                                                                               li, False)
+        k = int(ns)
+        onset, length = onset[:k].to(torch.int64), length[:k].to(torch.int64)
+        v = table[onset + length, length - 1]                   # k x K: the chosen spans under every category
+        if lw is not None and not include_weight:
+            v = v + lw.double()[None, :]
+        v = torch.nan_to_num(v, nan=-math.inf, posinf=math.inf, neginf=-math.inf)
+        ix = torch.arange(K, device=v.device)[None, :].expand_as(v)
+        free = torch.where(v == v.max(1, keepdim=True).values, ix, K).min(1).values if k else onset.new_zeros(0)
+    return {"onset": onset, "length": length, "category": category[:k].to(torch.int64), "score": seg[:k],
+            "path_score": ps, "link": link[:k], "context_free_category": free.to(torch.int64)}
+
+
+def count_transitions(categories_per_recording, K):
+    """``(trans_counts K x K, init_counts K)`` in float64 on the CPU:
+    ``trans_counts[i, j]`` is how often a segment of category j follows one of
+    category i inside a recording, ``init_counts[k]`` how many recordings start
+    with k.  ``categories_per_recording`` is a list of per-recording category
+    lists in time order; empty recordings count nothing.  A pure function."""
+    K = int(K)
+    tc = torch.zeros(K, K, dtype=torch.float64)
+    ic = torch.zeros(K, dtype=torch.float64)
+    for cats in categories_per_recording:
+        cats = [int(c) for c in cats]
+        if any(c < 0 or c >= K for c in cats):
+            raise ValueError(f"count_transitions: categories must lie in 0 .. {K - 1}")
+        if cats:
+            ic[cats[0]] += 1.0
+        for a, b in zip(cats[:-1], cats[1:]):
+            tc[a, b] += 1.0
+    return tc, ic
+
+
+def refit_transitions(segment_fn, recordings, model, n_iter, pseudo_count):
+    """Viterbi training of a ``TransitionModel`` on uncut recordings: per
+    iteration ``segment_fn(recording, model)`` (a ``segment_frames(...,
+    transitions=model)`` result) segments every recording, the category
+    bigrams of the paths are counted (``count_transitions``) and the model is
+    set to ``(counts + pseudo_count)`` normalised per row (the same for the
+    initial distribution; a row whose total is zero is kept).  Returns the
+    summed path score of every iteration's segmentation, ``n_iter`` floats:
+    entry i is the score under the model iteration i started from;
+    ``model.last_counts`` keeps the final iteration's ``(trans, init)`` counts."""
+    c = float(pseudo_count)
+    totals = []
+    for _ in range(int(n_iter)):
+        total, cats = 0.0, []
+        for rec in recordings:
+            out = segment_fn(rec, model)
+            total += float(out["path_score"])
+            cats.append(out["category"].tolist())
+        tc, ic = count_transitions(cats, model.K)
+        t, i = tc + c, ic + c
+        old_t, old_i = model.log_trans.double().exp().cpu(), model.log_init.double().exp().cpu()
+        rs = t.sum(1, keepdim=True)
+        trans = torch.where(rs > 0, t / rs.clamp_min(1e-300), old_t)
+        init = i / i.sum() if float(i.sum()) > 0 else old_i
+        model.set_probabilities(trans, init)
+        model.last_counts = (tc, ic)
+        totals.append(total)
+    return totals
 
 
 def _tempered_posterior(table, d_min, gap, seg_bonus, temperature, want_table):

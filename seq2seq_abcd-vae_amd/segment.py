@@ -30,7 +30,16 @@ frames ``s .. s + d - 1`` is written as samples ``s hop .. (s + d - 1) hop +
 loader turns into exactly d frames again.  The loader pads each segment at its
 own edges, so the frames nearest a boundary differ from the whole-recording
 frames this script scored: ``classify.py`` on the result can disagree with
-``category_ix`` there."""
+``category_ix`` there.
+
+``--transitions transitions.csv`` (what ``sequence.py`` wrote) makes the
+categories of consecutive segments a first-order chain inside the dynamic
+programme, so the matrix moves boundaries as well as labels; the table then
+also holds ``transition_score`` (the log initial or transition probability paid
+on entering the segment), ``context_free_category_ix`` (the span's label
+without the chain) and ``changed``.  ``--refit_transitions N`` runs N rounds of
+Viterbi training of the matrix on the recordings first and writes it to
+``--transitions_out``."""
 import os
 import sys
 
@@ -45,6 +54,8 @@ from modules import _native, segmentation
 
 COLUMNS = ("onset", "offset", "input_path", "data_type", "speaker", "label", "category_ix", "length", "segment_score")
 POSTERIOR_COLUMNS = ("onset_posterior", "offset_posterior", "span_posterior")   # appended by --posteriors
+SYNTAX_COLUMNS = ("transition_score", "context_free_category_ix", "changed")      # appended by --transitions
+TRANSITION_COLUMNS = ("from_ix", "to_ix", "probability", "expected_count")       # sequence.py's transitions.csv
 RECORDING_COLUMNS = ("input_path", "n_frames", "n_segments", "path_score", "log_evidence", "expected_segments")
 
 
@@ -91,9 +102,10 @@ def covered_frames(n_frames, onsets, offsets, fs, frame, hop, centering=True):
 
 
 def segment_rows(input_path, onset, length, category, score, fs, frame, hop, centering, total, data_type="segmented",
-                 speaker=float("nan"), posteriors=None):
+                 speaker=float("nan"), posteriors=None, syntax=None):
     """The table rows of one recording's segments (frame units -> seconds);
-    ``posteriors``: the three per-segment lists of POSTERIOR_COLUMNS."""
+    ``posteriors``: the three per-segment lists of POSTERIOR_COLUMNS;
+    ``syntax``: (link, context-free category) per segment for SYNTAX_COLUMNS."""
     rows = []
     for i, (s, d, k, v) in enumerate(zip(onset, length, category, score)):
         on, off = frames_to_samples(s, d, frame, hop, centering, total)
@@ -102,19 +114,29 @@ def segment_rows(input_path, onset, length, category, score, fs, frame, hop, cen
                      "segment_score": float(v)})
         if posteriors is not None:
             rows[-1].update({c: float(p[i]) for c, p in zip(POSTERIOR_COLUMNS, posteriors)})
+        if syntax is not None:
+            link, free = syntax
+            rows[-1].update({"transition_score": float(link[i]), "context_free_category_ix": int(free[i]),
+                             "changed": int(int(free[i]) != int(k))})
     return rows
 
 
-def write_segments(save_path, rows, posteriors=False, recordings_out=None, recordings=(), curves=None):
+def write_segments(save_path, rows, posteriors=False, recordings_out=None, recordings=(), curves=None, syntax=False,
+                   transitions_out=None, transitions=None):
     """Writes the annotation table (an existing file is kept as .prev, nothing
     partial is left behind) and, with ``posteriors``, its three extra columns,
     the per-recording table and the per-recording curve files ({path: dict of
-    arrays}) in the same replacement.  Returns the number of rows."""
-    df = pd.DataFrame(rows, columns=list(COLUMNS) + (list(POSTERIOR_COLUMNS) if posteriors else []))
+    arrays}) in the same replacement; with ``syntax`` the SYNTAX_COLUMNS, and
+    ``transitions`` (a table in TRANSITION_COLUMNS) to ``transitions_out``.
+    Returns the number of rows."""
+    df = pd.DataFrame(rows, columns=list(COLUMNS) + (list(POSTERIOR_COLUMNS) if posteriors else []) +
+                      (list(SYNTAX_COLUMNS) if syntax else []))
     with cli.replacing_outputs() as tmp:
         df.to_csv(tmp(save_path), index=False)
         if recordings_out is not None:
             pd.DataFrame(list(recordings), columns=list(RECORDING_COLUMNS)).to_csv(tmp(recordings_out), index=False)
+        if transitions_out is not None:
+            transitions.to_csv(tmp(transitions_out), index=False)
         for path, arrays in (curves or {}).items():
             with open(tmp(path), "wb") as f:
                 np.savez(f, **arrays)
@@ -138,13 +160,17 @@ class Segmenter(classify.Classifier):
     """A trained ABCD checkpoint opened for segmentation."""
 
     def segment_recording(self, frames, max_length, min_length=1, log_weight=None, gap=None, seg_bonus=0.0,
-                          speaker=None, posteriors=False, temperature=1.0):
+                          speaker=None, posteriors=False, temperature=1.0, transitions=None):
         """``segmentation.segment_frames`` of one recording's frames under the
-        categories' prototypes (of ``speaker`` when the decoder embeds speakers)."""
+        categories' prototypes (of ``speaker`` when the decoder embeds speakers);
+        ``transitions``: a TransitionModel for the programme with category
+        transitions."""
         if self.decoder.embed_speaker is not None and speaker is None:
             raise ValueError("this decoder embeds speakers: a speaker index is required")
         protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(max_length))
         extra = dict(posteriors=True, temperature=temperature) if posteriors else {}
+        if transitions is not None:
+            extra["transitions"] = transitions
         return segmentation.segment_frames(self.decoder, protos, frames.to(self.device), max_length,
                                            min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus,
                                            **extra)
@@ -191,7 +217,23 @@ def get_parameters(argv=None):
     p.add_argument("--recordings_out", type=str, default=None,
                    help="with --posteriors: csv with input_path, n_frames, n_segments, path_score, log_evidence, "
                         "expected_segments per recording")
+    p.add_argument("--transitions", type=str, default=None,
+                   help="a transitions.csv as sequence.py writes it: the categories of consecutive segments follow "
+                        "this matrix inside the dynamic programme (initial distribution: softmax of the prior's log "
+                        "weights); appends transition_score, context_free_category_ix and changed")
+    p.add_argument("--refit_transitions", type=int, default=0,
+                   help="iterations of Viterbi training of the matrix on the recordings before the final cut "
+                        "(0: none); starts from --transitions, or from the context-free matrix")
+    p.add_argument("--transitions_out", type=str, default=None,
+                   help="where --refit_transitions writes the refitted matrix (transitions.csv's columns)")
     a = p.parse_args(argv)
+    if a.refit_transitions < 0:
+        p.error("--refit_transitions must not be negative")
+    if (a.refit_transitions > 0) != (a.transitions_out is not None):
+        p.error("--refit_transitions and --transitions_out go together")
+    if a.posteriors and (a.transitions is not None or a.refit_transitions > 0):
+        p.error("--transitions / --refit_transitions cannot be combined with --posteriors: posteriors under a "
+                "transition model are not available")
     if not a.posterior_temperature > 0:
         p.error("--posterior_temperature must be positive")
     if not a.posteriors and (a.posterior_temperature != 1.0 or a.curves_dir is not None
@@ -212,7 +254,7 @@ def get_parameters(argv=None):
 def main(argv=None):
     a = get_parameters(argv)
     save_path = a.save_path or os.path.join(a.input_root, "segmented.csv")
-    for path in (save_path, a.gap_model_out, a.recordings_out):
+    for path in (save_path, a.gap_model_out, a.recordings_out, a.transitions_out):
         if path and os.path.dirname(path):
             os.makedirs(os.path.dirname(path), exist_ok=True)
     if a.curves_dir:
@@ -251,8 +293,12 @@ def main(argv=None):
             gap_model = (torch.from_numpy(z["mu"]), torch.from_numpy(z["log_var"]))
 
     lw = seg.log_weight(a.prior, len(table) if a.entire_data_size is None else a.entire_data_size)
-    rows, recordings, curves = [], [], {}
-    for path in paths:
+    syntax = a.transitions is not None or a.refit_transitions > 0
+    model, trans_table, prepared = None, None, {}
+
+    def prepare(path):
+        if path in prepared:
+            return prepared[path]
         fs, frame, hop, total, frames = featurise(path)
         d_min = max(a.min_length, min_loadable_length(frame, hop, centering))
         if d_min > a.min_length:
@@ -265,9 +311,39 @@ def main(argv=None):
             gap = torch.full((frames.shape[0],), float(a.gap_score), device=seg.device)
         elif gap_model is not None:
             gap = segmentation.gap_scores(frames, *gap_model)
-        out = seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
-                                    seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
-                                    temperature=a.posterior_temperature)
+        got = (fs, frame, hop, total, frames, d_min, gap)
+        if a.refit_transitions > 0:     # the training passes and the final cut share the features
+            prepared[path] = got
+        return got
+
+    def cut(path, transitions=None, got=None):
+        _, _, _, _, frames, d_min, gap = got or prepare(path)
+        return seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
+                                     seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
+                                     temperature=a.posterior_temperature, transitions=transitions)
+
+    if syntax:
+        import sequence
+        from modules.sequence import TransitionModel
+        K = int(lw.numel())
+        model = TransitionModel.from_log_weight(lw)
+        if a.transitions is not None:
+            model.set_probabilities(sequence.load_transitions(a.transitions, K), torch.softmax(lw.double(), 0))
+        if a.refit_transitions > 0:
+            totals = segmentation.refit_transitions(cut, paths, model, a.refit_transitions, 1.0 / K)
+            for i, v in enumerate(totals):
+                print(f"refit iteration {i}: summed path score {v:.6f}", file=sys.stderr)
+            ft, tt = np.divmod(np.arange(K * K), K)
+            trans_table = pd.DataFrame({"from_ix": ft, "to_ix": tt,
+                                        "probability": model.log_trans.double().exp().reshape(-1).cpu().numpy(),
+                                        "expected_count": model.last_counts[0].reshape(-1).cpu().numpy()},
+                                       columns=list(TRANSITION_COLUMNS))
+
+    rows, recordings, curves = [], [], {}
+    for path in paths:
+        got = prepare(path)
+        fs, frame, hop, total, frames, d_min, _ = got
+        out = cut(path, model, got)
         if not bool(out["path_score"] > float("-inf")):
             print(f"{path}: no cover of its {frames.shape[0]} frames by segments of {d_min} .. {a.max_length} "
                   "frames (give a gap score or model)", file=sys.stderr)
@@ -278,7 +354,8 @@ def main(argv=None):
         rows += segment_rows(path, out["onset"].tolist(), out["length"].tolist(), out["category"].tolist(),
                              out["score"].tolist(), fs, frame, hop, centering, total, data_type=data_type,
                              speaker=speaker,
-                             posteriors=[out[c].tolist() for c in POSTERIOR_COLUMNS] if a.posteriors else None)
+                             posteriors=[out[c].tolist() for c in POSTERIOR_COLUMNS] if a.posteriors else None,
+                             syntax=(out["link"].tolist(), out["context_free_category"].tolist()) if syntax else None)
         if a.posteriors:
             recordings.append({"input_path": path, "n_frames": int(frames.shape[0]), "n_segments": len(out["onset"]),
                                "path_score": float(out["path_score"]), "log_evidence": float(out["log_evidence"]),
@@ -289,7 +366,7 @@ def main(argv=None):
                                                               log_evidence=float(out["log_evidence"]), fs=fs, hop=hop)
     _native.op_status.sync("segment")
     write_segments(save_path, rows, posteriors=a.posteriors, recordings_out=a.recordings_out, recordings=recordings,
-                   curves=curves)
+                   curves=curves, syntax=syntax, transitions_out=a.transitions_out, transitions=trans_table)
     return save_path
 
 
