@@ -4,11 +4,12 @@
     ABCD_PARITY_DUMP=<dir> python -m pytest -m gpu tests
     python scripts/parity_table.py <dir>
 
-tests/test_gpu_edges.py, test_gpu_fullshape.py, test_gpu_prod.py,
-test_gpu_sampler_widths.py and test_gpu_philox.py write the errors they
+tests/test_gpu_edges.py, test_gpu_ladder.py, test_gpu_fullshape.py,
+test_gpu_prod.py, test_gpu_sampler_widths.py and test_gpu_philox.py write the errors they
 observed (the HIP path against the float64 / fp32 oracle or the reference's
 fixtures) into <dir> when ABCD_PARITY_DUMP is set; this puts them into one
-table next to the tolerances derived from them.  A section <dir> holds no
+table next to the tolerances derived from them (what other test files
+dump there belongs to other tables and is left alone).  A section <dir> holds no
 figures for (a run of some of the files) keeps what the table has.
 """
 import glob
@@ -26,12 +27,14 @@ def sig(x, n=3):
 
 
 def main(src):
+    import edge_cases as E
     import test_gpu_edges as TE
     import test_gpu_fullshape as TF
+    import test_gpu_ladder as TL
     import test_gpu_prod as TP
     import test_gpu_sampler_widths as TS
-    edges, full, prod, samp, philox = {}, {}, {}, {}, {}
-    worst_ratio, samp_ratio = {}, {}
+    edges, full, prod, samp, philox, ladder = {}, {}, {}, {}, {}, {}
+    worst_ratio, samp_ratio, ladder_ratio = {}, {}, {}
     for path in sorted(glob.glob(os.path.join(src, "*.json"))):
         name = os.path.basename(path)[:-5]
         with open(path) as f:
@@ -46,6 +49,19 @@ def main(src):
                         key = f"{name[len('samp-'):]}: {k}"
                         samp_ratio[key] = max(samp_ratio.get(key, 0.0), sig(a / max(b, 1e-30)))
             samp[name[len("samp-"):]] = rows
+        elif name.startswith("ladder-"):
+            rows = {}
+            for r in d:
+                k = r["tensor"]
+                rows[k] = [sig(r["e32_rel"]), sig(r["e_hip_rel"]), sig(r["e32_blk"]), sig(r["e_hip_blk"]), r["R"]]
+                for a, b in ((r["e_hip_rel"], r["e32_rel"]), (r["e_hip_blk"], r["e32_blk"])):
+                    raised = TL.R_ENCODER if name.startswith("ladder-enc-") else TL.R_TENSOR
+                    # past the default bound, or a raised tensor's ratio past 4 inside the bound's 1e-7
+                    if a > TL.bound(TL.R_DEFAULT, b) or (k in raised and a > TL.R_DEFAULT * b):
+                        key = ("encoder: " if name.startswith("ladder-enc-") else "") + k
+                        if sig(a / max(b, 1e-30)) > ladder_ratio.get(key, (0.0, ""))[0]:
+                            ladder_ratio[key] = (sig(a / max(b, 1e-30)), name[len("ladder-"):])
+            ladder[name[len("ladder-"):]] = rows
         elif name.startswith("philox-"):
             philox[name[len("philox-"):]] = {k: (sig(v) if isinstance(v, float) else v) for k, v in d[0].items()}
         elif name.startswith("fullshape-"):
@@ -56,7 +72,7 @@ def main(src):
             prod[name[len("prod-"):]] = dict(
                 worst=sig(d["worst"]), **({"clip": sig(d["clip"])} if "clip" in d else {}),
                 tensors={k: {m: sig(x) for m, x in v.items()} for k, v in d.get("tensors", {}).items()})
-        else:
+        elif name.split("-")[0] in E.CASES:  # test_gpu_edges.py: <case>-<widths> / <case>-frames
             rows = {}
             for r in d:
                 rows[r["tensor"]] = [sig(r["e32_rel"]), sig(r["e_hip_rel"]), sig(r["e32_blk"]), sig(r["e_hip_blk"]), r["R"]]
@@ -81,6 +97,20 @@ def main(src):
             "worst_e_hip": {m: max(r[i] for rows in edges.values() for r in rows.values())
                             for m, i in (("rel", 1), ("blk", 3))} if edges else {},
             "cases": edges,
+        },
+        "ladder": {
+            "file": "tests/test_gpu_ladder.py (widths, routes and references: tests/ladder_cases.py)",
+            "reference": "enc-*: torch.nn.LSTM / GRU in float64, e32 the same module in fp32; dec-* / frames-*: the "
+                         "float64 oracle step, e32 the fp32 oracle",
+            "columns": ["e32_rel", "e_hip_rel", "e32_blk", "e_hip_blk", "R"],
+            "bound": "e_hip <= R * e32 + 1e-7, and e_hip <= %g whatever R" % TL.HARD,
+            "R_default": TL.R_DEFAULT, "R_tensor": TL.R_TENSOR, "R_encoder": TL.R_ENCODER,
+            "worst_ratio_past_R_default": {k: list(v) for k, v in sorted(ladder_ratio.items())},
+            "R_note": "R is raised only for a tensor whose e_hip / e32 went past 4, to at most 2 x its own worst "
+                      "ratio. " + TL.R_NOTE,
+            "worst_e_hip": {m: max(r[i] for rows in ladder.values() for r in rows.values())
+                            for m, i in (("rel", 1), ("blk", 3))} if ladder else {},
+            "cases": ladder,
         },
         "full_shape": {
             "file": "tests/test_gpu_fullshape.py", "reference": "the fp32 oracle (oracle.train_step)",
@@ -122,7 +152,7 @@ def main(src):
     if os.path.isfile(out):
         with open(out) as f:
             old = json.load(f)
-        for sec, got in (("edge_cases", edges), ("full_shape", full), ("prod_fixtures", prod),
+        for sec, got in (("edge_cases", edges), ("ladder", ladder), ("full_shape", full), ("prod_fixtures", prod),
                          ("sampler_widths", samp or philox)):
             if not got and sec in old:
                 table[sec] = old[sec]
@@ -131,7 +161,8 @@ def main(src):
     text = re.sub(r"\[\s+([^\[\]{}]*?)\s+\]", lambda m: "[" + re.sub(r"\s+", " ", m.group(1)) + "]", text)
     with open(out, "w") as f:
         f.write(text + "\n")
-    print(out, os.path.getsize(out), "bytes;", len(edges), "edge cases,", len(full), "full-shape,", len(prod), "prod")
+    print(out, os.path.getsize(out), "bytes;", len(edges), "edge cases,", len(ladder), "ladder cases,", len(full),
+          "full-shape,", len(prod), "prod")
 
 
 if __name__ == "__main__":

@@ -1037,9 +1037,11 @@ __global__ __launch_bounds__(256) void dec_fwd_persist(PDecFwdArgs a) {
         if (col < F) {
           mu = am[0][0][g] + bm;
           lv = al[0][0][g] + bl;
-          const float e = k == 0 ? epre[g]
-                                 : (a.eps ? a.eps[rr * F + col]
-                                          : philox_normal(a.seed, a.offset + (uint64_t)rr * F + col));
+          // (b < bs: a row past the step's batch has no eps row -- a read there runs past the block)
+          const float e = k == 0   ? epre[g]
+                          : b >= bs ? 0.f
+                          : a.eps  ? a.eps[rr * F + col]
+                                   : philox_normal(a.seed, a.offset + (uint64_t)rr * F + col);
           x = mu + __expf(0.5f * lv) * e;
         }
         if (b < bs && a.feedback && b < next_bs) {
@@ -2681,6 +2683,7 @@ int persist_encoder_bwd(hipStream_t s, int G, const PBwdArgs& a, bool* launched)
   if (G == 4) {
     if (pd == 16) return launch_bwd<4, 16>(s, a, launched);
     if (pd == 4) return launch_bwd<4, 4>(s, a, launched);
+    // (never reached: 4 H / 16 is a multiple of 4 at every H the encoder accepts, so pd >= 4 for the LSTM)
     return launch_bwd<4, 1>(s, a, launched);
   }
   if (pd == 16) return launch_bwd<3, 16>(s, a, launched);
