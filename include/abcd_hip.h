@@ -772,6 +772,70 @@ int abcd_span_chain_viterbi(const double* table, long ld_k, long N, int D, int K
                             size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Segmentation posteriors under the chain: the sum half of
+ * abcd_span_chain_viterbi.  table, gap, seg_bonus, d_min,
+ * log_trans and log_init are those of abcd_span_chain_viterbi; scale is 1 /
+ * temperature and multiplies every term (table entries, gap, seg_bonus,
+ * log_trans, log_init) in fp64 after widening, so scale = 1 is exact.  Below
+ * T, gap, bonus, lt, li are the multiplied terms; a candidate that is NaN or
+ * -inf is excluded; LAE is logaddexp, LSE the log-sum-exp over the admissible
+ * candidates, -inf over none:
+ *   G[0] = 0,  G[n] = G[n-1] + gap[n-1]         (gap NULL: -inf for n >= 1)
+ *   aW[0][k] = aV[0][k] = -inf
+ *   aU[n][k] = LAE(G[n] + li[k], LSE_k' (aW[n][k'] + lt[k'][k])),  n < N;  aU[N][k] = -inf
+ *   aV[n][k] = bonus + LSE_{d_min <= d <= min(D,n)} (aU[n-d][k] + T[n,d,k])
+ *   aW[n][k] = LAE(aW[n-1][k] + gap[n-1], aV[n][k])
+ *   log_z    = LAE(G[N], LSE_k aW[N][k])
+ *   bW[N][k] = 0, bG[N] = 0, bU[N][k] = -inf;  n = N-1 .. 0:
+ *   bU[n][k] = LSE_{d_min <= d <= min(D,N-n)} (T[n+d,d,k] + bonus + bW[n+d][k])
+ *   bW[n][k] = LAE(gap[n] + bW[n+1][k], LSE_k'' (lt[k][k''] + bU[n][k'']))
+ *   bG[n]    = LAE(gap[n] + bG[n+1], LSE_k (li[k] + bU[n][k]))          (bG[0] = log_z)
+ *   post_k[n K + k]             = exp(aU[n][k] + bU[n][k] - log_z)   a segment of k starts at frame n
+ *   post_k[(N + 1) K + n K + k] = exp(aV[n][k] + bW[n][k] - log_z)   a segment of k ends before frame n
+ *   gap_post[n] = exp(LAE(G[n] + bG[n+1], LSE_k (aW[n][k] + bW[n+1][k])) + gap[n] - log_z),  n < N;  [N] = 0
+ *   init_counts[k]          = sum_{n < N} exp(G[n] + li[k] + bU[n][k] - log_z)
+ *   trans_counts[k' K + k]  = sum_{n < N} exp(aW[n][k'] + lt[k'][k] + bU[n][k] - log_z)
+ *   span_post[e ld_post + d - 1] = sum_k exp(aU[e-d][k] + T[e,d,k] + bonus + bW[e][k] - log_z)
+ * (span_post: N + 1 rows, zero outside d_min .. min(D, e)).  log_z = -inf (no
+ * cover) makes every posterior and count 0.  lattice is five planes of (N + 1)
+ * x K doubles (aU, aV, aW, bU, bW), lattice_g two of N + 1 (G, bG); both may be
+ * NULL and then live in the workspace.  trans_counts (K x K, row stride K) and
+ * init_counts (K) come together or not at all; span_post may be NULL.
+ * One workgroup (abcd_span_chain_viterbi's launch widths: 1024 threads up to K
+ * = 256, 256 above) runs both sweeps, the counts and the per-frame posteriors
+ * in one launch: lanes over k, the waves split d and k', each wave keeps a
+ * (maximum, sum of exp(c - maximum)) pair per k, the pairs meet in LDS and one
+ * thread per k joins them in wave order.  The backward sweep walks the starts
+ * n = N-1 .. 0 (T[n+d, d, :] is contiguous).  log_trans is resident in LDS up
+ * to K = 128 at a row stride of K + 1 floats and streamed above; streamed, the
+ * backward chain phase gives each wave whole rows of log_trans
+ * (abcd_span_chain_posterior_plan says which, with the launch width and the
+ * LDS bytes; it is a pure function).  A count entry is owned by one thread
+ * and summed in n order.  span_post comes from a second, ordinary kernel,
+ * launched only when asked for.  No atomics, no device-global word, nothing is
+ * allocated, two calls agree bit for bit.  +inf in the table is outside the
+ * contract.
+ * Limits: those of abcd_span_chain_viterbi (1 <= K <= 1024, (N + 1) D ld_k <
+ * 2^31); the workspace query returns 0 beyond them.  ABCD_EINVAL (decided on
+ * the host before any launch, nothing is written): those limits, d_min outside
+ * 1 .. D, scale not finite or not positive, ld_k < K, ld_trans < K, ld_post < D
+ * with span_post given, exactly one of the two count buffers, a NULL among
+ * table, log_trans, log_init, log_z, post_k and gap_post while N > 0, a missing
+ * or short workspace.  N = 0 writes log_z = 0, bW[0][k] = G[0] = bG[0] = 0,
+ * -inf in the other four planes and zero posteriors and counts (each where not
+ * NULL) and reads nothing.
+ *
+ * No timing or dispatch id is assigned to these entry points.
+ * ---------------------------------------------------------------------- */
+int abcd_span_chain_posterior_plan(int K, int D, int* resident, int* threads, size_t* lds_bytes);
+size_t abcd_span_chain_posterior_workspace_bytes(long N, int D, int K);
+int abcd_span_chain_posterior(const double* table, long ld_k, long N, int D, int K, int d_min, const float* gap,
+                              double seg_bonus, double scale, const float* log_trans, long ld_trans,
+                              const float* log_init, double* log_z, double* lattice, double* lattice_g,
+                              double* post_k, double* gap_post, double* trans_counts, double* init_counts,
+                              double* span_post, long ld_post, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Time-warped scoring: a segment aligned to a prototype.  abcd_pairwise_nll
  * scores frame t against step t; here the T_proto steps of prototype p are the
  * states of a left-to-right HMM and frame t of segment b is emitted by state

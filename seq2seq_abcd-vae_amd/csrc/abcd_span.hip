@@ -744,6 +744,314 @@ __global__ __launch_bounds__(SC_THREADS) void span_chain(
   }
 }
 
+// The sum form of span_chain: one workgroup, one launch, both
+// sweeps over the state (frame, last category), span_chain's launch widths and
+// partition.  Every term (table, gap, bonus, log_trans, log_init) is multiplied
+// by `scale` in fp64 after widening; bonus arrives multiplied.
+//   forward   aU / aV / aW as U / Vs / W of span_chain with LSE for max and LAE
+//             for the two-term maxima
+//   backward  n = N-1 .. 0 over STARTS: bU[n][k] = LSE_d (T[n+d,d,k] + bonus +
+//             bW[n+d][k]) reads K contiguous doubles per d, as the forward does;
+//             bW[n][k] = LAE(gap[n] + bW[n+1][k], LSE_k'' (lt[k][k''] + bU[n][k'']))
+// A thread folds its candidates in ascending order into a pair (maximum, sum of
+// exp(c - maximum)): one exp per candidate.  The waves' pairs of a k meet in
+// LDS and thread k joins them in wave order, one log per k and phase.  RES
+// keeps log_trans in LDS at a row stride of K + 1 floats: the forward reads
+// along a row, the backward chain phase (lanes over the ROW index k) at stride
+// K + 1 = 1 mod 64 banks.  Streamed (K > SC_RES_K), the backward chain phase
+// gives each wave whole rows instead, lanes over k'' (contiguous in global
+// memory), and joins the lanes' pairs by an xor butterfly: the join is
+// symmetric, so every lane holds the same bits.
+// The five lattice planes ((N + 1) x K each) and G / bG live in global memory;
+// the workgroup reads its own stores a barrier later.  The expected counts are
+// accumulated in the backward sweep (log_z is known by then) into the caller's
+// buffers: thread (wave w, lane l) owns the entries (k' = w mod waves, k = l mod
+// 64), the forward chain phase's partition, and adds to them in n order.  After
+// the sweeps: bG (the per-frame LSE over k by one wave per frame, then the
+// recursion over n by wave 0, 64 frames loaded at a time), the gap posterior
+// (one wave per frame) and the per-(frame, category) posteriors, elementwise.
+// No atomics, no device-global word.
+DEV void pair_fold(double& m, double& z, double c) {  // c = NaN or -inf: excluded
+  if (c > -INFINITY) {
+    const double w = exp(-fabs(m - c));  // m = -inf: 0
+    if (c > m) { z = z * w + 1.0; m = c; } else z += w;
+  }
+}
+
+// the parts pairs of k at pm / pz [i K + k], joined in order; -inf over none
+DEV double pair_join(const double* pm, const double* pz, int parts, int K, int k) {
+  double M = -INFINITY;
+  for (int i = 0; i < parts; ++i) M = fmax(M, pm[i * K + k]);
+  if (!(M > -INFINITY)) return -INFINITY;
+  double Z = 0.0;
+  for (int i = 0; i < parts; ++i) Z += pz[i * K + k] * exp(pm[i * K + k] - M);  // an empty pair: 0 * 0
+  return M + log(Z);
+}
+
+// every lane's pair joined across the wave (all lanes end with the same bits); -inf over none
+DEV double pair_wave_lse(double m, double z) {
+  for (int o = 32; o > 0; o >>= 1) {
+    const double m2 = __shfl_xor(m, o, 64), z2 = __shfl_xor(z, o, 64);
+    const double M = fmax(m, m2);
+    if (M > -INFINITY) {
+      const double a = z * exp(m - M), b = z2 * exp(m2 - M);
+      z = (m >= m2) ? a + b : b + a;  // the same two operands in the same order on both lanes
+    }
+    m = M;
+  }
+  return m > -INFINITY ? m + log(z) : -INFINITY;
+}
+
+static size_t span_chain_fb_lds(int K) {
+  const int nw = span_chain_waves(K);
+  // bW / aW of the step, log_init, bU of the step, aW[n] for the counts; the waves' pairs; RES: the matrix
+  return (size_t)K * (4 + 2 * nw) * sizeof(double) + (K <= SC_RES_K ? (size_t)K * (K + 1) * sizeof(float) : 0);
+}
+
+template <bool RES>
+__global__ __launch_bounds__(SC_THREADS) void span_chain_fb(
+    const double* __restrict__ T, long ldk, long N, int D, int K, int dmin, const float* __restrict__ gap, double bonus,
+    double scale, const float* __restrict__ LT, long ldt, const float* __restrict__ LI, double* log_z, double* lat,
+    double* latg, double* post_k, double* gap_post, double* tc, double* ic) {
+  extern __shared__ __attribute__((aligned(16))) double sc_lds[];
+  __shared__ double lz_sh;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nt = blockDim.x, nw = nt >> 6;
+  double* const Wc = sc_lds;         // aW[n] (forward), bW[n + 1] (backward)
+  double* const Li = Wc + K;         // scale * log_init
+  double* const Bu = Li + K;         // bU[n]
+  double* const Aw = Bu + K;         // aW[n], for the counts
+  double* const pm = Aw + K;         // the waves' pairs, nw x K each
+  double* const pz = pm + nw * K;
+  const float* const lt = (const float*)(pz + nw * K);  // RES: K rows of K + 1
+  const int lds_t = K + 1;
+  const long P = (N + 1) * K;
+  double* const aU = lat;
+  double* const aV = lat + P;
+  double* const aW = lat + 2 * P;
+  double* const bU = lat + 3 * P;
+  double* const bW = lat + 4 * P;
+  double* const Gp = latg;
+  double* const bG = latg + (N + 1);
+  auto trans = [&](int kp, int k) {  // scale * log_trans[kp][k]
+    return scale * (double)(RES ? lt[kp * lds_t + k] : LT[(long)kp * ldt + k]);
+  };
+  for (int k = tid; k < K; k += nt) {
+    const double li = scale * (double)LI[k];
+    Wc[k] = -INFINITY;
+    Li[k] = li;
+    aU[k] = li > -INFINITY ? li : -INFINITY;  // G[0] = 0 and aW[0] = -inf: the initial term
+    aV[k] = -INFINITY;
+    aW[k] = -INFINITY;
+  }
+  if (RES) {
+    float* const dst = (float*)(pz + nw * K);
+    for (int i = tid; i < K * K; i += nt) dst[(i / K) * lds_t + i % K] = LT[(long)(i / K) * ldt + i % K];
+  }
+  if (tid == 0) Gp[0] = 0.0;
+  __syncthreads();
+  // ---- forward
+  double G = 0.0;
+  for (long n = 1; n <= N; ++n) {
+    const double gv = gap ? scale * (double)gap[n - 1] : -INFINITY;
+    G = G + gv;
+    const int dmax = (int)min((long)D, n);
+    for (int k = lane; k < K; k += 64) {
+      double m = -INFINITY, z = 0.0;
+      const double* const Trow = T + (n * D - 1) * ldk + k;  // + d ldk
+      const double* const Urow = aU + n * K + k;              // - d K
+#pragma unroll 4
+      for (int d = dmin + w; d <= dmax; d += nw) pair_fold(m, z, Urow[-(long)d * K] + scale * Trow[(long)d * ldk]);
+      pm[w * K + k] = m;
+      pz[w * K + k] = z;
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nt) {
+      const double seg = pair_join(pm, pz, nw, K, k);
+      const double av = seg > -INFINITY ? bonus + seg : -INFINITY;
+      const double aw = logaddexp_d(Wc[k] + gv, av);
+      Wc[k] = aw;
+      aV[n * K + k] = av;
+      aW[n * K + k] = aw;
+      if (n == N) aU[n * K + k] = -INFINITY;  // no segment starts at N
+    }
+    if (tid == 0) Gp[n] = G;
+    __syncthreads();
+    if (n == N) break;
+    for (int k = lane; k < K; k += 64) {
+      double m = -INFINITY, z = 0.0;
+#pragma unroll 4
+      for (int kp = w; kp < K; kp += nw) pair_fold(m, z, Wc[kp] + trans(kp, k));
+      pm[w * K + k] = m;
+      pz[w * K + k] = z;
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nt) aU[n * K + k] = logaddexp_d(G + Li[k], pair_join(pm, pz, nw, K, k));
+    __syncthreads();
+  }
+  if (tid == 0) {  // log_z = LAE(G[N], LSE_k aW[N][k])
+    double m = -INFINITY, z = 0.0;
+    for (int k = 0; k < K; ++k) pair_fold(m, z, Wc[k]);
+    const double lz = logaddexp_d(G, m > -INFINITY ? m + log(z) : -INFINITY);
+    lz_sh = lz;
+    *log_z = lz;
+  }
+  __syncthreads();
+  const double lz = lz_sh;
+  // ---- backward
+  for (int k = tid; k < K; k += nt) {
+    Wc[k] = 0.0;
+    bW[N * K + k] = 0.0;
+    bU[N * K + k] = -INFINITY;
+  }
+  if (tc) {  // each entry by the thread that adds to it below
+    for (int kp = w; kp < K; kp += nw)
+      for (int k = lane; k < K; k += 64) tc[(long)kp * K + k] = 0.0;
+    for (int k = tid; k < K; k += nt) ic[k] = 0.0;
+  }
+  __syncthreads();
+  const bool count = tc && lz > -INFINITY;
+  for (long n = N - 1; n >= 0; --n) {
+    const double gv = gap ? scale * (double)gap[n] : -INFINITY;
+    const int dmax = (int)min((long)D, N - n);
+    for (int k = lane; k < K; k += 64) {
+      double m = -INFINITY, z = 0.0;
+      const double* const Trow = T + (n * D - 1) * ldk + k;  // + d (D + 1) ldk: row n + d, column d - 1
+      const double* const Brow = bW + n * K + k;              // + d K
+#pragma unroll 4
+      for (int d = dmin + w; d <= dmax; d += nw)
+        pair_fold(m, z, (scale * Trow[(long)d * (D + 1) * ldk] + bonus) + Brow[(long)d * K]);
+      pm[w * K + k] = m;
+      pz[w * K + k] = z;
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nt) {
+      const double bu = pair_join(pm, pz, nw, K, k);
+      Bu[k] = bu;
+      bU[n * K + k] = bu;
+      if (count) {
+        Aw[k] = aW[n * K + k];
+        const double c = (Gp[n] + Li[k]) + bu - lz;
+        if (c > -INFINITY) ic[k] += exp(c);
+      }
+    }
+    __syncthreads();
+    int parts = nw;
+    if (RES) {
+      for (int k = lane; k < K; k += 64) {  // lanes over the row index
+        double m = -INFINITY, z = 0.0;
+#pragma unroll 4
+        for (int kq = w; kq < K; kq += nw) pair_fold(m, z, trans(k, kq) + Bu[kq]);
+        pm[w * K + k] = m;
+        pz[w * K + k] = z;
+      }
+    } else {
+      parts = 1;
+      for (int k = w; k < K; k += nw) {  // a wave per row, lanes along it
+        double m = -INFINITY, z = 0.0;
+        for (int kq = lane; kq < K; kq += 64) pair_fold(m, z, trans(k, kq) + Bu[kq]);
+        const double v = pair_wave_lse(m, z);
+        if (lane == 0) { pm[k] = v; pz[k] = 1.0; }
+      }
+    }
+    if (count) {
+      for (int kp = w; kp < K; kp += nw) {
+        const double a = Aw[kp];
+        if (!(a > -INFINITY)) continue;  // uniform over the wave
+        for (int k = lane; k < K; k += 64) {
+          const double c = (a + trans(kp, k)) + Bu[k] - lz;
+          if (c > -INFINITY) tc[(long)kp * K + k] += exp(c);
+        }
+      }
+    }
+    __syncthreads();
+    for (int k = tid; k < K; k += nt) {
+      const double bw = logaddexp_d(gv + Wc[k], pair_join(pm, pz, parts, K, k));
+      Wc[k] = bw;
+      bW[n * K + k] = bw;
+    }
+    __syncthreads();
+  }
+  // ---- bG: LSE_k (li[k] + bU[n][k]) per frame, then the recursion over n
+  if (tid == 0) bG[N] = 0.0;
+  for (long n = w; n < N; n += nw) {
+    double m = -INFINITY, z = 0.0;
+    for (int k = lane; k < K; k += 64) pair_fold(m, z, Li[k] + bU[n * K + k]);
+    const double v = pair_wave_lse(m, z);
+    if (lane == 0) bG[n] = v;
+  }
+  __syncthreads();
+  if (w == 0) {
+    double b = 0.0;
+    for (long base = N - 1; base >= 0; base -= 64) {
+      const long at = base - lane;
+      const double q = at >= 0 ? bG[at] : -INFINITY;
+      const double g = (at >= 0 && gap) ? scale * (double)gap[at] : -INFINITY;
+      double mine = -INFINITY;
+      for (int j = 0; j < 64; ++j) {
+        b = logaddexp_d(__shfl(g, j, 64) + b, __shfl(q, j, 64));
+        if (lane == j) mine = b;
+      }
+      if (at >= 0) bG[at] = mine;
+    }
+  }
+  __syncthreads();
+  // ---- the posteriors
+  const bool reach = lz > -INFINITY;
+  for (long n = w; n <= N; n += nw) {
+    double gp = 0.0;
+    if (n < N && gap && reach) {
+      double m = -INFINITY, z = 0.0;
+      for (int k = lane; k < K; k += 64) pair_fold(m, z, aW[n * K + k] + bW[(n + 1) * K + k]);
+      const double in = logaddexp_d(Gp[n] + bG[n + 1], pair_wave_lse(m, z));
+      const double c = in + scale * (double)gap[n] - lz;
+      if (c > -INFINITY) gp = exp(c);
+    }
+    if (lane == 0) gap_post[n] = gp > 0.0 ? gp : 0.0;
+  }
+  for (long i = tid; i < P; i += nt) {
+    double on = 0.0, en = 0.0;
+    if (reach) {
+      on = exp(aU[i] + bU[i] - lz);
+      en = exp(aV[i] + bW[i] - lz);
+    }
+    post_k[i] = on > 0.0 ? on : 0.0;  // a NaN (inf - inf, outside the contract) reads as 0
+    post_k[P + i] = en > 0.0 ? en : 0.0;
+  }
+}
+
+// span_post[e, d - 1] = sum_k exp(aU[e-d][k] + scale T[e,d,k] + bonus + bW[e][k] - log_z), 0 outside d_min ..
+// min(D, e): 16 lanes per entry, strided over k, their sums joined by an xor butterfly
+__global__ __launch_bounds__(256) void span_chain_post_table(const double* __restrict__ T, long ldk, long N, int D,
+                                                             int K, int dmin, double bonus, double scale,
+                                                             const double* __restrict__ lat,
+                                                             const double* __restrict__ log_z,
+                                                             double* __restrict__ span_post, long ldp) {
+  const long at = (long)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int j = threadIdx.x & 15;
+  const bool in = at < (N + 1) * D;  // whole 16-lane groups leave the sums together
+  const long e = in ? at / D : 0;
+  const int d = in ? (int)(at - e * D) + 1 : 1;
+  const double lz = *log_z;
+  double v = 0.0;
+  if (in && d >= dmin && d <= e && lz > -INFINITY) {
+    const double* const Trow = T + (e * D + d - 1) * ldk;
+    const double* const Urow = lat + (e - d) * K;
+    const double* const Brow = lat + 4 * (N + 1) * K + e * K;
+    for (int k = j; k < K; k += 16) {
+      const double c = ((Urow[k] + scale * Trow[k]) + bonus) + Brow[k];
+      if (c > -INFINITY) v += exp(c - lz);
+    }
+  }
+  for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if (in && j == 0) span_post[e * ldp + d - 1] = v > 0.0 ? v : 0.0;
+}
+
+__global__ __launch_bounds__(256) void span_fill_value(double* __restrict__ p, long n, double v) {
+  const long at = (long)blockIdx.x * 256 + threadIdx.x;
+  if (at < n) p[at] = v;
+}
+
 static bool span_shape_ok(long N, int D) {
   return D >= 1 && D <= SP_MAX_D && N >= 0 && N < (1L << 31) && (N + 1) * (long)D < (1L << 31);
 }
@@ -980,5 +1288,80 @@ extern "C" int abcd_span_chain_viterbi(const double* table, long ld_k, long N, i
                                                                seg_length, seg_cat, seg_score, seg_link, W_out, U,
                                                                back_d, back_k);
   ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int abcd_span_chain_posterior_plan(int K, int D, int* resident, int* threads, size_t* lds_bytes) {
+  ABCD_REQUIRE(K >= 1 && K <= SC_MAX_K && D >= 1 && D <= SP_MAX_D);
+  if (resident) *resident = K <= SC_RES_K;
+  if (threads) *threads = 64 * span_chain_waves(K);
+  if (lds_bytes) *lds_bytes = span_chain_fb_lds(K);
+  return 0;
+}
+
+extern "C" size_t abcd_span_chain_posterior_workspace_bytes(long N, int D, int K) {
+  if (K < 1 || K > SC_MAX_K || !span_table_ok(N, D, K)) return 0;
+  // the five lattice planes and G / bG, for the caller that keeps none
+  return ((size_t)N + 1) * (5 * (size_t)K + 2) * sizeof(double) + 256;
+}
+
+extern "C" int abcd_span_chain_posterior(const double* table, long ld_k, long N, int D, int K, int d_min,
+                                         const float* gap, double seg_bonus, double scale, const float* log_trans,
+                                         long ld_trans, const float* log_init, double* log_z, double* lattice,
+                                         double* lattice_g, double* post_k, double* gap_post, double* trans_counts,
+                                         double* init_counts, double* span_post, long ld_post, void* ws,
+                                         size_t ws_bytes, void* stream) {
+  ABCD_REQUIRE(K >= 1 && K <= SC_MAX_K && span_table_ok(N, D, ld_k) && d_min >= 1 && d_min <= D);
+  ABCD_REQUIRE(scale > 0.0 && scale < INFINITY);  // NaN fails both
+  ABCD_REQUIRE(ld_k >= K && ld_trans >= K);
+  ABCD_REQUIRE(!span_post || ld_post >= D);
+  ABCD_REQUIRE(!trans_counts == !init_counts);  // the counts come together or not at all
+  ABCD_REQUIRE(N == 0 || (table && log_trans && log_init && log_z && post_k && gap_post));
+  const size_t need = abcd_span_chain_posterior_workspace_bytes(N, D, K);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  if (N == 0) {  // the empty cover: log_z = 0, bW[0] = G[0] = bG[0] = 0, the other planes -inf, zeros; nothing is read
+    if (log_z) ABCD_TRY(hipMemsetAsync(log_z, 0, sizeof(double), s));
+    if (lattice) {
+      span_fill_value<<<cdiv(4 * K, 256), 256, 0, s>>>(lattice, 4 * K, -INFINITY);
+      ABCD_CHECK_LAUNCH();
+      ABCD_TRY(hipMemsetAsync(lattice + 4 * K, 0, K * sizeof(double), s));
+    }
+    if (lattice_g) ABCD_TRY(hipMemsetAsync(lattice_g, 0, 2 * sizeof(double), s));
+    if (post_k) ABCD_TRY(hipMemsetAsync(post_k, 0, 2 * K * sizeof(double), s));
+    if (gap_post) ABCD_TRY(hipMemsetAsync(gap_post, 0, sizeof(double), s));
+    if (trans_counts) {
+      ABCD_TRY(hipMemsetAsync(trans_counts, 0, (size_t)K * K * sizeof(double), s));
+      ABCD_TRY(hipMemsetAsync(init_counts, 0, K * sizeof(double), s));
+    }
+    if (span_post) ABCD_TRY(hipMemsetAsync(span_post, 0, D * sizeof(double), s));
+    return 0;
+  }
+  static bool attr = false;
+  if (!attr) {
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain_fb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)span_chain_fb_lds(SC_RES_K)));
+    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain_fb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                 (int)std::max(span_chain_fb_lds(SC_WIDE_K), span_chain_fb_lds(SC_MAX_K))));
+    attr = true;
+  }
+  double* lat = lattice ? lattice : (double*)ws;
+  double* latg = lattice_g ? lattice_g : (double*)ws + 5 * (N + 1) * K;
+  const double bonus = seg_bonus * scale;
+  const int threads = 64 * span_chain_waves(K);
+  if (K <= SC_RES_K)
+    span_chain_fb<true><<<1, threads, span_chain_fb_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, bonus, scale,
+                                                                  log_trans, ld_trans, log_init, log_z, lat, latg,
+                                                                  post_k, gap_post, trans_counts, init_counts);
+  else
+    span_chain_fb<false><<<1, threads, span_chain_fb_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, bonus, scale,
+                                                                   log_trans, ld_trans, log_init, log_z, lat, latg,
+                                                                   post_k, gap_post, trans_counts, init_counts);
+  ABCD_CHECK_LAUNCH();
+  if (span_post) {
+    span_chain_post_table<<<cdiv((N + 1) * D, 16), 256, 0, s>>>(table, ld_k, N, D, K, d_min, bonus, scale, lat, log_z,
+                                                                span_post, ld_post);
+    ABCD_CHECK_LAUNCH();
+  }
   return 0;
 }

@@ -182,6 +182,12 @@ _SIGS = {
     "abcd_span_chain_viterbi": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_double, c_void_p,
                                         c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "abcd_span_chain_posterior_plan": (c_int, [c_int, c_int, _P(c_int), _P(c_int), _P(c_size_t)]),
+    "abcd_span_chain_posterior_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "abcd_span_chain_posterior": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_double, c_double,
+                                          c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_size_t,
+                                          c_void_p]),
     "abcd_warp_nll_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "abcd_warp_nll": (c_int, [_P(Packed), c_void_p, c_int, c_int, c_void_p, c_long, c_void_p, c_long, c_void_p,
                               _P(c_double), c_int, c_int, c_void_p, c_long, c_void_p, c_size_t, c_void_p]),

@@ -35,9 +35,10 @@ operator                   replaces (reference)                            C ent
 ``abcd::span_posterior``   (none: posteriors over all covers by segments)  ``abcd_span_posterior``
 ``abcd::span_table``       (none: span scores of every category)           ``abcd_span_table``
 ``abcd::span_chain_viterbi`` (none: the best cover under a category chain) ``abcd_span_chain_viterbi``
+``abcd::span_chain_posterior`` (none: posteriors and counts under the chain) ``abcd_span_chain_posterior``
 =========================  ==============================================  =========================================
 
-The last fourteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
+The last fifteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -1197,6 +1198,76 @@ def _(table, d_min, gap, seg_bonus, log_trans, log_init, want_w):
 _forward_only(span_chain_viterbi, "span_chain_viterbi")
 
 
+@torch.library.custom_op("abcd::span_chain_posterior", mutates_args=())
+def span_chain_posterior(table: Tensor, d_min: int, gap: Optional[Tensor], seg_bonus: float, scale: float,
+                         log_trans: Tensor, log_init: Tensor, want_counts: bool, want_table: bool) -> List[Tensor]:
+    """-> [log_z (0-d, fp64), lattice (5 x (N + 1) x K: aU, aV, aW, bU, bW),
+    lattice_g (2 x (N + 1): G, bG), post_k (2 x (N + 1) x K: onset, end),
+    gap_post (N + 1), trans_counts (K x K), init_counts (K), span_post ((N + 1)
+    x D)], fp64 each: the semi-Markov forward-backward over (frame, last
+    category) on span_table's table under span_chain_viterbi's d_min, gap,
+    seg_bonus, log_trans and log_init, every term multiplied by ``scale`` (1 /
+    temperature) in fp64 (abcd_span_chain_posterior).  The counts and
+    span_post are empty tensors unless asked for.  An uncoverable recording
+    gives log_z = -inf and zeros."""
+    for t in (table, log_trans, log_init):
+        N.require_gpu(t)
+    if table.dim() != 3 or min(table.shape) < 1:
+        raise ValueError(f"span_chain_posterior: table must be N + 1 x D x K, got {tuple(table.shape)}")
+    n, D, K = int(table.shape[0]) - 1, int(table.shape[1]), int(table.shape[2])
+    d_min, scale = int(d_min), float(scale)
+    if d_min < 1 or d_min > D:
+        raise ValueError(f"span_chain_posterior: d_min must lie in 1 .. {D}, got {d_min}")
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"span_chain_posterior: scale must be positive and finite, got {scale}")
+    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
+        raise ValueError(f"span_chain_posterior: log_trans must be {K} x {K} and log_init hold {K} entries, got "
+                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
+    if K > 1024:
+        raise ValueError(f"span_chain_posterior: at most 1024 categories, got {K}")
+    L_ = N.lib()
+    nbytes = L_.abcd_span_chain_posterior_workspace_bytes(n, D, K)
+    if nbytes == 0:
+        raise N.HipError(f"span_chain_posterior: unsupported shape ({_TABLE_LIMIT}); N = {n}, D = {D}, K = {K}")
+    dev = table.device
+    tb = table.double().contiguous()
+    lt, ldt = _rows(log_trans.float())
+    li = log_init.float().contiguous()
+    g = None
+    if gap is not None:
+        N.require_gpu(gap)
+        if gap.numel() != n:
+            raise ValueError(f"span_chain_posterior: gap must hold {n} entries, got {gap.numel()}")
+        g = gap.float().contiguous()
+    ws = N.workspace(nbytes, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    log_z = torch.empty((), **f64)
+    lattice, lattice_g = torch.empty(5, n + 1, K, **f64), torch.empty(2, n + 1, **f64)
+    post_k, gap_post = torch.empty(2, n + 1, K, **f64), torch.empty(n + 1, **f64)
+    tc = torch.empty((K, K) if want_counts else (0, 0), **f64)
+    ic = torch.empty(K if want_counts else 0, **f64)
+    span = torch.empty((n + 1, D) if want_table else (0, 0), **f64)
+    N.check(L_.abcd_span_chain_posterior(N.ptr(tb), K, n, D, K, d_min, N.ptr(g), float(seg_bonus), scale, N.ptr(lt),
+                                         ldt, N.ptr(li), N.ptr(log_z), N.ptr(lattice), N.ptr(lattice_g),
+                                         N.ptr(post_k), N.ptr(gap_post), N.ptr(tc) if want_counts else None,
+                                         N.ptr(ic) if want_counts else None, N.ptr(span) if want_table else None, D,
+                                         N.ptr(ws), ws.numel(), N.stream()), "span chain posterior")
+    return [log_z, lattice, lattice_g, post_k, gap_post, tc, ic, span]
+
+
+@span_chain_posterior.register_fake
+def _(table, d_min, gap, seg_bonus, scale, log_trans, log_init, want_counts, want_table):
+    n, D, K = table.shape[0] - 1, table.shape[1], table.shape[2]
+
+    def e(*shape):
+        return table.new_empty(shape, dtype=torch.float64)
+    return [e(), e(5, n + 1, K), e(2, n + 1), e(2, n + 1, K), e(n + 1), e(K, K) if want_counts else e(0, 0),
+            e(K) if want_counts else e(0), e(n + 1, D) if want_table else e(0, 0)]
+
+
+_forward_only(span_chain_posterior, "span_chain_posterior")
+
+
 # ----------------------------------------------------------------------------
 # time-warped scoring: segments aligned to prototypes (forward-only)
 # ----------------------------------------------------------------------------
@@ -1361,7 +1432,8 @@ _forward_only(griffin_lim, "griffin_lim")
 OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sampler_sample_bwd", "sampler_kl",
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
        "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
-       "warp_nll", "warp_path", "span_evidence", "span_posterior", "span_table", "span_chain_viterbi")
+       "warp_nll", "warp_path", "span_evidence", "span_posterior", "span_table", "span_chain_viterbi",
+       "span_chain_posterior")
 
 
 def registered() -> Sequence[str]:

@@ -15,7 +15,11 @@ gap and span posteriors over every cover and the recording's log evidence
 ``segment_frames(transitions=...)`` puts a first-order chain over the
 categories of consecutive segments inside the programme
 (``ops.span_table`` / ``ops.span_chain_viterbi``); ``count_transitions`` and
-``refit_transitions`` fit that chain on uncut recordings by Viterbi training."""
+``refit_transitions`` fit that chain on uncut recordings by Viterbi training.
+``segment_chain_posteriors`` is the sum half of that programme (onset, end,
+gap, span and label posteriors, the evidence and the expected bigram counts
+under the chain, ``ops.span_chain_posterior``) and ``refit_transitions_em``
+fits the chain by EM on those counts."""
 import math
 
 import torch
@@ -115,16 +119,22 @@ def _segment_chain(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_b
     with torch.no_grad():
         table, _, _ = decoder.span_table(prototypes, frames, D, log_weight=lw if include_weight else None)
         g = None if gap is None else torch.as_tensor(gap, device=frames.device).float()
-        ps, ns, onset, length, category, seg, link, _ = ops.span_chain_viterbi(table, d_min, g, float(seg_bonus), lt,
-                                                                               li, False)
-        k = int(ns)
-        onset, length = onset[:k].to(torch.int64), length[:k].to(torch.int64)
-        v = table[onset + length, length - 1]                   # k x K: the chosen spans under every category
-        if lw is not None and not include_weight:
-            v = v + lw.double()[None, :]
-        v = torch.nan_to_num(v, nan=-math.inf, posinf=math.inf, neginf=-math.inf)
-        ix = torch.arange(K, device=v.device)[None, :].expand_as(v)
-        free = torch.where(v == v.max(1, keepdim=True).values, ix, K).min(1).values if k else onset.new_zeros(0)
+        return _chain_cut(table, d_min, g, seg_bonus, lt, li, lw, include_weight, K)
+
+
+def _chain_cut(table, d_min, g, seg_bonus, lt, li, lw, include_weight, K):
+    """The best cover of span_table's ``table`` under the chain and the dict
+    ``segment_frames(transitions=...)`` returns (inside ``torch.no_grad()``)."""
+    ps, ns, onset, length, category, seg, link, _ = ops.span_chain_viterbi(table, d_min, g, float(seg_bonus), lt, li,
+                                                                           False)
+    k = int(ns)
+    onset, length = onset[:k].to(torch.int64), length[:k].to(torch.int64)
+    v = table[onset + length, length - 1]                   # k x K: the chosen spans under every category
+    if lw is not None and not include_weight:
+        v = v + lw.double()[None, :]
+    v = torch.nan_to_num(v, nan=-math.inf, posinf=math.inf, neginf=-math.inf)
+    ix = torch.arange(K, device=v.device)[None, :].expand_as(v)
+    free = torch.where(v == v.max(1, keepdim=True).values, ix, K).min(1).values if k else onset.new_zeros(0)
     return {"onset": onset, "length": length, "category": category[:k].to(torch.int64), "score": seg[:k],
             "path_score": ps, "link": link[:k], "context_free_category": free.to(torch.int64)}
 
@@ -168,14 +178,120 @@ def refit_transitions(segment_fn, recordings, model, n_iter, pseudo_count):
             total += float(out["path_score"])
             cats.append(out["category"].tolist())
         tc, ic = count_transitions(cats, model.K)
-        t, i = tc + c, ic + c
-        old_t, old_i = model.log_trans.double().exp().cpu(), model.log_init.double().exp().cpu()
-        rs = t.sum(1, keepdim=True)
-        trans = torch.where(rs > 0, t / rs.clamp_min(1e-300), old_t)
-        init = i / i.sum() if float(i.sum()) > 0 else old_i
-        model.set_probabilities(trans, init)
-        model.last_counts = (tc, ic)
+        _m_step(model, tc, ic, c)
         totals.append(total)
+    return totals
+
+
+def _m_step(model, tc, ic, c):
+    """``(counts + c)`` normalised per row into ``model`` (a row whose total is zero is kept); keeps the counts."""
+    t, i = tc + c, ic + c
+    old_t, old_i = model.log_trans.double().exp().cpu(), model.log_init.double().exp().cpu()
+    rs = t.sum(1, keepdim=True)
+    trans = torch.where(rs > 0, t / rs.clamp_min(1e-300), old_t)
+    init = i / i.sum() if float(i.sum()) > 0 else old_i
+    model.set_probabilities(trans, init)
+    model.last_counts = (tc, ic)
+
+
+def segment_chain_posteriors(decoder, prototypes, frames, max_length, transitions, min_length=1, log_weight=None,
+                             include_weight=False, gap=None, seg_bonus=0.0, temperature=1.0, want_counts=False,
+                             want_table=False, with_segments=False):
+    """The sum half of ``segment_frames(transitions=...)``: the posterior over
+    EVERY labelled cover of ``frames`` under the transition model, from a
+    semi-Markov forward-backward over (frame, last category) in fp64 on the
+    device (``ops.span_chain_posterior``).  The table is built once
+    (``decoder.span_table``, without ``log_weight`` unless ``include_weight``,
+    as ``segment_frames`` does).  A dict of
+
+    ``log_evidence``        0-d float64; the TEMPERED model's when ``temperature != 1``
+    ``onset`` ``end`` ``gap``   N + 1 float64 each, summed over the categories (``segment_posteriors``' keys)
+    ``onset_by_category``   (N + 1) x K: P(a segment of k starts at frame n)
+    ``end_by_category``     (N + 1) x K: P(a segment of k ends before frame n)
+    ``frame_category``      N x K: P(frame n lies in a segment of k)
+    ``expected_segments``   0-d: the sum of ``end``
+    ``category_usage``      K: the expected number of segments of each category
+    ``no_segment``          0-d: P(the recording holds no segment at all)
+    ``trans_counts`` ``init_counts``  with ``want_counts``: the expected bigram (K x K) and first-label (K) counts
+    ``span``                with ``want_table``: (N + 1) x max_length, P(frames e - d .. e - 1 are one segment)
+
+    ``temperature`` divides every term (table, gap, bonus, log_trans,
+    log_init) in float64 inside the kernel.  ``with_segments`` also runs
+    ``ops.span_chain_viterbi`` on the same table (at temperature 1) and adds
+    ``segmentation``, what ``segment_frames(..., transitions=...)`` returns bit
+    for bit, and per chosen segment ``span_posterior`` (summed over the
+    categories) and ``label_posterior`` (this span with this label)."""
+    N.require_gpu(frames)
+    D, d_min, T = int(max_length), int(min_length), float(temperature)
+    if not 1 <= d_min <= D:
+        raise ValueError(f"segment_chain_posteriors: 1 <= min_length <= max_length, got {d_min} and {D}")
+    if not (T > 0.0 and math.isfinite(T)):
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    lt, li = _chain_of(transitions, frames.device)
+    K = int(prototypes[2].shape[1])
+    if lt.shape[0] != K:
+        raise ValueError(f"segment_chain_posteriors: the transition model has {lt.shape[0]} categories, the "
+                         f"prototypes {K}")
+    lw = None if log_weight is None else torch.as_tensor(log_weight, device=frames.device).float().reshape(-1)
+    s = 1.0 / T
+    with torch.no_grad():
+        table, _, _ = decoder.span_table(prototypes, frames, D, log_weight=lw if include_weight else None)
+        g = None if gap is None else torch.as_tensor(gap, device=frames.device).float()
+        want_span = bool(want_table or with_segments)
+        log_z, lat, lat_g, post_k, gap_post, tc, ic, span = ops.span_chain_posterior(
+            table, d_min, g, float(seg_bonus), s, lt, li, bool(want_counts), want_span)
+        n = int(frames.shape[0])
+        onset_k, end_k = post_k[0], post_k[1]
+        reach = bool(log_z > -math.inf)
+        no_seg = torch.exp(lat_g[0, n] - log_z) if reach else torch.zeros((), dtype=torch.float64, device=frames.device)
+        out = {"log_evidence": log_z, "onset": onset_k.sum(1), "end": end_k.sum(1), "gap": gap_post,
+               "onset_by_category": onset_k, "end_by_category": end_k,
+               "frame_category": torch.cumsum(onset_k - end_k, 0)[:n], "expected_segments": end_k.sum(),
+               "category_usage": end_k.sum(0), "no_segment": no_seg}
+        if want_counts:
+            out.update(trans_counts=tc, init_counts=ic)
+        if want_table:
+            out["span"] = span
+        if with_segments:
+            seg = _chain_cut(table, d_min, g, seg_bonus, lt, li, lw, include_weight, K)
+            on, ln = seg["onset"], seg["length"]
+            end = on + ln
+            out["segmentation"] = seg
+            out["span_posterior"] = span[end, ln - 1]
+            if reach and on.numel():
+                c = (lat[0][on, seg["category"]] + s * seg["score"] + s * float(seg_bonus)
+                     + lat[4][end, seg["category"]] - log_z)
+                out["label_posterior"] = torch.nan_to_num(torch.exp(c), nan=0.0)
+            else:
+                out["label_posterior"] = torch.zeros(on.numel(), dtype=torch.float64, device=frames.device)
+    return out
+
+
+def refit_transitions_em(posterior_fn, recordings, model, n_iter, pseudo_count, temperature=1.0):
+    """EM (Baum-Welch) of a ``TransitionModel`` on uncut recordings, the sum
+    form of ``refit_transitions``: per iteration ``posterior_fn(recording,
+    model)`` (a ``segment_chain_posteriors(..., want_counts=True)`` result)
+    gives every recording's expected counts and log evidence, the counts are
+    summed and the M-step is ``refit_transitions``' own.  Returns per
+    iteration ``temperature * sum log_evidence + pseudo_count * (sum of the
+    finite log_trans and log_init)`` under the model the iteration started
+    from; ``model.last_counts`` keeps the final iteration's ``(trans, init)``
+    expected counts (float64, on the CPU)."""
+    c, T = float(pseudo_count), float(temperature)
+    totals = []
+    for _ in range(int(n_iter)):
+        tc = torch.zeros(model.K, model.K, dtype=torch.float64)
+        ic = torch.zeros(model.K, dtype=torch.float64)
+        ev = 0.0
+        for rec in recordings:
+            out = posterior_fn(rec, model)
+            ev += float(out["log_evidence"])
+            tc += torch.as_tensor(out["trans_counts"]).double().cpu()
+            ic += torch.as_tensor(out["init_counts"]).double().cpu()
+        lt, li = model.log_trans.double().cpu(), model.log_init.double().cpu()
+        pen = float(lt[torch.isfinite(lt)].sum() + li[torch.isfinite(li)].sum())
+        totals.append(T * ev + c * pen)
+        _m_step(model, tc, ic, c)
     return totals
 
 

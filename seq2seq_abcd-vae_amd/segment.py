@@ -39,7 +39,11 @@ also holds ``transition_score`` (the log initial or transition probability paid
 on entering the segment), ``context_free_category_ix`` (the span's label
 without the chain) and ``changed``.  ``--refit_transitions N`` runs N rounds of
 Viterbi training of the matrix on the recordings first and writes it to
-``--transitions_out``."""
+``--transitions_out``; ``--refit_method em`` makes those rounds EM on the expected
+bigram counts over every labelled cover instead.  ``--chain_posteriors`` sums
+over every labelled cover under the chain (``segmentation.segment_chain_posteriors``)
+and appends ``onset_posterior``, ``offset_posterior``, ``span_posterior`` and
+``label_posterior``: how far to trust each cut and each label."""
 import os
 import sys
 
@@ -55,6 +59,8 @@ from modules import _native, segmentation
 COLUMNS = ("onset", "offset", "input_path", "data_type", "speaker", "label", "category_ix", "length", "segment_score")
 POSTERIOR_COLUMNS = ("onset_posterior", "offset_posterior", "span_posterior")   # appended by --posteriors
 SYNTAX_COLUMNS = ("transition_score", "context_free_category_ix", "changed")      # appended by --transitions
+CHAIN_POSTERIOR_COLUMNS = POSTERIOR_COLUMNS + ("label_posterior",)                # appended by --chain_posteriors
+REFIT_METHODS = ("viterbi", "em")
 TRANSITION_COLUMNS = ("from_ix", "to_ix", "probability", "expected_count")       # sequence.py's transitions.csv
 RECORDING_COLUMNS = ("input_path", "n_frames", "n_segments", "path_score", "log_evidence", "expected_segments")
 
@@ -102,10 +108,11 @@ def covered_frames(n_frames, onsets, offsets, fs, frame, hop, centering=True):
 
 
 def segment_rows(input_path, onset, length, category, score, fs, frame, hop, centering, total, data_type="segmented",
-                 speaker=float("nan"), posteriors=None, syntax=None):
+                 speaker=float("nan"), posteriors=None, syntax=None, chain_posteriors=None):
     """The table rows of one recording's segments (frame units -> seconds);
     ``posteriors``: the three per-segment lists of POSTERIOR_COLUMNS;
-    ``syntax``: (link, context-free category) per segment for SYNTAX_COLUMNS."""
+    ``syntax``: (link, context-free category) per segment for SYNTAX_COLUMNS;
+    ``chain_posteriors``: the four per-segment lists of CHAIN_POSTERIOR_COLUMNS."""
     rows = []
     for i, (s, d, k, v) in enumerate(zip(onset, length, category, score)):
         on, off = frames_to_samples(s, d, frame, hop, centering, total)
@@ -118,19 +125,23 @@ def segment_rows(input_path, onset, length, category, score, fs, frame, hop, cen
             link, free = syntax
             rows[-1].update({"transition_score": float(link[i]), "context_free_category_ix": int(free[i]),
                              "changed": int(int(free[i]) != int(k))})
+        if chain_posteriors is not None:
+            rows[-1].update({c: float(p[i]) for c, p in zip(CHAIN_POSTERIOR_COLUMNS, chain_posteriors)})
     return rows
 
 
 def write_segments(save_path, rows, posteriors=False, recordings_out=None, recordings=(), curves=None, syntax=False,
-                   transitions_out=None, transitions=None):
+                   transitions_out=None, transitions=None, chain_posteriors=False):
     """Writes the annotation table (an existing file is kept as .prev, nothing
     partial is left behind) and, with ``posteriors``, its three extra columns,
     the per-recording table and the per-recording curve files ({path: dict of
     arrays}) in the same replacement; with ``syntax`` the SYNTAX_COLUMNS, and
-    ``transitions`` (a table in TRANSITION_COLUMNS) to ``transitions_out``.
+    ``transitions`` (a table in TRANSITION_COLUMNS) to ``transitions_out``;
+    with ``chain_posteriors`` the CHAIN_POSTERIOR_COLUMNS after those.
     Returns the number of rows."""
     df = pd.DataFrame(rows, columns=list(COLUMNS) + (list(POSTERIOR_COLUMNS) if posteriors else []) +
-                      (list(SYNTAX_COLUMNS) if syntax else []))
+                      (list(SYNTAX_COLUMNS) if syntax else []) +
+                      (list(CHAIN_POSTERIOR_COLUMNS) if chain_posteriors else []))
     with cli.replacing_outputs() as tmp:
         df.to_csv(tmp(save_path), index=False)
         if recordings_out is not None:
@@ -174,6 +185,17 @@ class Segmenter(classify.Classifier):
         return segmentation.segment_frames(self.decoder, protos, frames.to(self.device), max_length,
                                            min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus,
                                            **extra)
+
+    def chain_posteriors(self, frames, max_length, transitions, min_length=1, log_weight=None, gap=None,
+                         seg_bonus=0.0, speaker=None, **kw):
+        """``segmentation.segment_chain_posteriors`` of one recording's frames
+        under the categories' prototypes and the TransitionModel ``transitions``."""
+        if self.decoder.embed_speaker is not None and speaker is None:
+            raise ValueError("this decoder embeds speakers: a speaker index is required")
+        protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(max_length))
+        return segmentation.segment_chain_posteriors(self.decoder, protos, frames.to(self.device), max_length,
+                                                     transitions, min_length=min_length, log_weight=log_weight,
+                                                     gap=gap, seg_bonus=seg_bonus, **kw)
 
 
 def get_parameters(argv=None):
@@ -226,7 +248,20 @@ def get_parameters(argv=None):
                         "(0: none); starts from --transitions, or from the context-free matrix")
     p.add_argument("--transitions_out", type=str, default=None,
                    help="where --refit_transitions writes the refitted matrix (transitions.csv's columns)")
+    p.add_argument("--refit_method", type=str, default="viterbi", choices=REFIT_METHODS,
+                   help="how --refit_transitions counts bigrams: those of each recording's best path (viterbi) or "
+                        "the expected counts over every labelled cover (em); with em --transitions_out carries the "
+                        "expected counts in expected_count")
+    p.add_argument("--chain_posteriors", action="store_true",
+                   help="with --transitions / --refit_transitions: also sum over every labelled segmentation under "
+                        "the chain and append onset_posterior, offset_posterior, span_posterior and label_posterior; "
+                        "--posterior_temperature, --curves_dir (which also holds each frame's most probable category "
+                        "and its probability) and --recordings_out apply")
     a = p.parse_args(argv)
+    if a.chain_posteriors and a.transitions is None and a.refit_transitions <= 0:
+        p.error("--chain_posteriors needs --transitions or --refit_transitions")
+    if a.refit_method != "viterbi" and a.refit_transitions <= 0:
+        p.error("--refit_method needs --refit_transitions")
     if a.refit_transitions < 0:
         p.error("--refit_transitions must not be negative")
     if (a.refit_transitions > 0) != (a.transitions_out is not None):
@@ -236,8 +271,8 @@ def get_parameters(argv=None):
                 "transition model are not available")
     if not a.posterior_temperature > 0:
         p.error("--posterior_temperature must be positive")
-    if not a.posteriors and (a.posterior_temperature != 1.0 or a.curves_dir is not None
-                             or a.recordings_out is not None):
+    if not (a.posteriors or a.chain_posteriors) and (a.posterior_temperature != 1.0 or a.curves_dir is not None
+                                                     or a.recordings_out is not None):
         p.error("--posterior_temperature, --curves_dir and --recordings_out need --posteriors")
     if a.max_length < 1 or a.max_length > 16383:
         p.error("--max_length must lie in 1 .. 16383")
@@ -322,6 +357,11 @@ def main(argv=None):
                                      seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
                                      temperature=a.posterior_temperature, transitions=transitions)
 
+    def posterior(path, transitions, got=None, **kw):
+        _, _, _, _, frames, d_min, gap = got or prepare(path)
+        return seg.chain_posteriors(frames, a.max_length, transitions, min_length=d_min, log_weight=lw, gap=gap,
+                                    seg_bonus=a.segment_bonus, speaker=a.speaker, **kw)
+
     if syntax:
         import sequence
         from modules.sequence import TransitionModel
@@ -329,10 +369,16 @@ def main(argv=None):
         model = TransitionModel.from_log_weight(lw)
         if a.transitions is not None:
             model.set_probabilities(sequence.load_transitions(a.transitions, K), torch.softmax(lw.double(), 0))
-        if a.refit_transitions > 0:
+        if a.refit_transitions > 0 and a.refit_method == "em":
+            totals = segmentation.refit_transitions_em(lambda path, m: posterior(path, m, want_counts=True), paths,
+                                                       model, a.refit_transitions, 1.0 / K)
+            for i, v in enumerate(totals):
+                print(f"refit iteration {i}: log posterior of the matrix {v:.6f}", file=sys.stderr)
+        elif a.refit_transitions > 0:
             totals = segmentation.refit_transitions(cut, paths, model, a.refit_transitions, 1.0 / K)
             for i, v in enumerate(totals):
                 print(f"refit iteration {i}: summed path score {v:.6f}", file=sys.stderr)
+        if a.refit_transitions > 0:
             ft, tt = np.divmod(np.arange(K * K), K)
             trans_table = pd.DataFrame({"from_ix": ft, "to_ix": tt,
                                         "probability": model.log_trans.double().exp().reshape(-1).cpu().numpy(),
@@ -343,7 +389,12 @@ def main(argv=None):
     for path in paths:
         got = prepare(path)
         fs, frame, hop, total, frames, d_min, _ = got
-        out = cut(path, model, got)
+        post = None
+        if a.chain_posteriors:
+            post = posterior(path, model, got, temperature=a.posterior_temperature, with_segments=True)
+            out = post["segmentation"]
+        else:
+            out = cut(path, model, got)
         if not bool(out["path_score"] > float("-inf")):
             print(f"{path}: no cover of its {frames.shape[0]} frames by segments of {d_min} .. {a.max_length} "
                   "frames (give a gap score or model)", file=sys.stderr)
@@ -355,7 +406,21 @@ def main(argv=None):
                              out["score"].tolist(), fs, frame, hop, centering, total, data_type=data_type,
                              speaker=speaker,
                              posteriors=[out[c].tolist() for c in POSTERIOR_COLUMNS] if a.posteriors else None,
-                             syntax=(out["link"].tolist(), out["context_free_category"].tolist()) if syntax else None)
+                             syntax=(out["link"].tolist(), out["context_free_category"].tolist()) if syntax else None,
+                             chain_posteriors=None if post is None else [
+                                 post["onset"][out["onset"]].tolist(),
+                                 post["end"][out["onset"] + out["length"]].tolist(),
+                                 post["span_posterior"].tolist(), post["label_posterior"].tolist()])
+        if post is not None:
+            recordings.append({"input_path": path, "n_frames": int(frames.shape[0]), "n_segments": len(out["onset"]),
+                               "path_score": float(out["path_score"]), "log_evidence": float(post["log_evidence"]),
+                               "expected_segments": float(post["expected_segments"])})
+            if a.curves_dir:
+                prob, label = post["frame_category"].max(1)
+                curves[curve_path(a.curves_dir, path)] = dict(
+                    onset=post["onset"].cpu().numpy(), end=post["end"].cpu().numpy(), gap=post["gap"].cpu().numpy(),
+                    frame_category=label.cpu().numpy(), frame_category_probability=prob.cpu().numpy(),
+                    log_evidence=float(post["log_evidence"]), fs=fs, hop=hop)
         if a.posteriors:
             recordings.append({"input_path": path, "n_frames": int(frames.shape[0]), "n_segments": len(out["onset"]),
                                "path_score": float(out["path_score"]), "log_evidence": float(out["log_evidence"]),
@@ -366,7 +431,8 @@ def main(argv=None):
                                                               log_evidence=float(out["log_evidence"]), fs=fs, hop=hop)
     _native.op_status.sync("segment")
     write_segments(save_path, rows, posteriors=a.posteriors, recordings_out=a.recordings_out, recordings=recordings,
-                   curves=curves, syntax=syntax, transitions_out=a.transitions_out, transitions=trans_table)
+                   curves=curves, syntax=syntax, transitions_out=a.transitions_out, transitions=trans_table,
+                   chain_posteriors=a.chain_posteriors)
     return save_path
 
 
