@@ -217,6 +217,14 @@ constexpr int SV_THREADS = 256;  // the widest launch; D <= SV_ONE_WAVE_D runs a
 constexpr int SV_ONE_WAVE_D = 256;
 constexpr int SV_PRE = 4;  // span entries per thread loaded one step ahead (D <= 4 x the launch width runs from registers)
 
+// (maximum, sum of exp(c - maximum)) with candidate c folded in: one exp per candidate
+DEV void pair_fold(double& m, double& z, double c) {  // c = NaN or -inf: excluded
+  if (c > -INFINITY) {
+    const double w = exp(-fabs(m - c));  // m = -inf: 0
+    if (c > m) { z = z * w + 1.0; m = c; } else z += w;
+  }
+}
+
 // One workgroup, one launch: V[n] for n = 1 .. N, then the backtrack.
 //   V[n] = max(V[n-1] + gap[n-1], max_{d_min <= d <= min(D, n)} (V[n-d] + span[n, d]) + bonus)
 // Lanes stride over d; each thread's candidates in ascending d under a strict
@@ -472,10 +480,7 @@ __global__ __launch_bounds__(SV_THREADS) void span_fb(const double* __restrict__
     double mo = ring[at], zo = PAIR ? ring2[at] : 0.0;
     if (d == D) { mo = -INFINITY; zo = 0.0; }  // the first to reach this start: the slot's earlier start is done
     if (PAIR) {
-      if (c > -INFINITY) {
-        const double w = exp(-fabs(mo - c));  // mo = -inf: 0
-        if (c > mo) { zo = zo * w + 1.0; mo = c; } else zo += w;
-      }
+      pair_fold(mo, zo, c);
       ring[at] = mo;
       ring2[at] = zo;
     } else {
@@ -771,13 +776,6 @@ __global__ __launch_bounds__(SC_THREADS) void span_chain(
 // recursion over n by wave 0, 64 frames loaded at a time), the gap posterior
 // (one wave per frame) and the per-(frame, category) posteriors, elementwise.
 // No atomics, no device-global word.
-DEV void pair_fold(double& m, double& z, double c) {  // c = NaN or -inf: excluded
-  if (c > -INFINITY) {
-    const double w = exp(-fabs(m - c));  // m = -inf: 0
-    if (c > m) { z = z * w + 1.0; m = c; } else z += w;
-  }
-}
-
 // the parts pairs of k at pm / pz [i K + k], joined in order; -inf over none
 DEV double pair_join(const double* pm, const double* pz, int parts, int K, int k) {
   double M = -INFINITY;
@@ -1070,27 +1068,62 @@ extern "C" size_t abcd_span_scores_workspace_bytes(long N, int D, int P) {
   return (size_t)D * (size_t)P * sizeof(double) + 256;  // O[p, d]
 }
 
+// What the three passes over the frames share, after an entry point's own requires (every failed require returns
+// ABCD_EINVAL, so their order is not seen): the requires on the frames, the prototypes and the workspace, the rows
+// e < D of each output that is there (`out`: span_lse or the table, by MODE), span_prefix and span_nll<MODE>.
+template <int MODE>
+static int span_pass(const float* x, long ld_x, long N, int F, int P, int D, int T_proto, const float* proto_mu,
+                     long ld_mu, const float* proto_lv, long ld_lv, const float* proto_offset_logits,
+                     const float* log_weight, double* out, long ld_k, double* span_score, int32_t* span_cat,
+                     long ld_span, void* ws, size_t ws_bytes, void* stream) {
+  ABCD_REQUIRE(P >= 1 && F >= 1 && T_proto >= D && ld_x >= F && ld_mu >= F && ld_lv >= F);
+  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits));
+  const size_t need = abcd_span_scores_workspace_bytes(N, D, P);  // 0: span_shape_ok fails
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  const long rows = std::min(N, (long)D - 1) + 1;
+  const bool best = span_score && span_cat;
+  if (MODE == SPAN_TABLE && out) {
+    span_table_fill<<<cdiv(rows * D * P, 256), 256, 0, s>>>(rows, D, P, out, ld_k);
+    ABCD_CHECK_LAUNCH();
+  }
+  if (best || (MODE == SPAN_LSE && out)) {  // neither: N = 0 with nowhere to write row 0
+    span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, MODE == SPAN_LSE ? out : nullptr,
+                                                  ld_span);
+    ABCD_CHECK_LAUNCH();
+  }
+  if (N == 0) return 0;
+  double* Otab = (double*)ws;
+  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
+  span_nll<MODE><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+                                                log_weight, span_score, span_cat, out, ld_span, ld_k);
+  ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+// hipFuncAttributeMaxDynamicSharedMemorySize of KERNEL, raised once
+template <auto KERNEL>
+static hipError_t raise_lds(size_t bytes) {
+  static bool done = false;
+  if (done) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  done = e == hipSuccess;
+  return e;
+}
+
+// one workgroup of span_chain's width with `lds` bytes: `resident` up to K = SC_RES_K, `streamed` above
+template <class... P, class... A>
+static void chain_launch(void (*resident)(P...), void (*streamed)(P...), int K, size_t lds, hipStream_t s, A... args) {
+  (K <= SC_RES_K ? resident : streamed)<<<1, 64 * span_chain_waves(K), lds, s>>>(args...);
+}
+
 extern "C" int abcd_span_scores(const float* x, long ld_x, long N, int F, int P, int D, int T_proto,
                                 const float* proto_mu, long ld_mu, const float* proto_lv, long ld_lv,
                                 const float* proto_offset_logits, const float* log_weight, double* span_score,
                                 int32_t* span_cat, long ld_span, void* ws, size_t ws_bytes, void* stream) {
-  ABCD_REQUIRE(span_shape_ok(N, D) && P >= 1 && F >= 1 && T_proto >= D);
-  ABCD_REQUIRE(ld_x >= F && ld_mu >= F && ld_lv >= F && ld_span >= D);
-  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits && span_score && span_cat));
-  const size_t need = abcd_span_scores_workspace_bytes(N, D, P);
-  ABCD_REQUIRE(need && ws && ws_bytes >= need);
-  if (!span_score || !span_cat) return 0;  // N = 0 with nowhere to write row 0
-  hipStream_t s = (hipStream_t)stream;
-  const long rows = std::min(N, (long)D - 1) + 1;
-  span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, nullptr, ld_span);
-  ABCD_CHECK_LAUNCH();
-  if (N == 0) return 0;
-  double* Otab = (double*)ws;
-  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<SPAN_MAX><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
-                                                    log_weight, span_score, span_cat, nullptr, ld_span, 0);
-  ABCD_CHECK_LAUNCH();
-  return 0;
+  ABCD_REQUIRE(ld_span >= D && (N == 0 || (span_score && span_cat)));
+  return span_pass<SPAN_MAX>(x, ld_x, N, F, P, D, T_proto, proto_mu, ld_mu, proto_lv, ld_lv, proto_offset_logits,
+                             log_weight, nullptr, 0, span_score, span_cat, ld_span, ws, ws_bytes, stream);
 }
 
 extern "C" size_t abcd_span_evidence_workspace_bytes(long N, int D, int P) {
@@ -1102,24 +1135,10 @@ extern "C" int abcd_span_evidence(const float* x, long ld_x, long N, int F, int 
                                   const float* proto_offset_logits, const float* log_weight, double* span_lse,
                                   double* span_score, int32_t* span_cat, long ld_span, void* ws, size_t ws_bytes,
                                   void* stream) {
-  ABCD_REQUIRE(span_shape_ok(N, D) && P >= 1 && F >= 1 && T_proto >= D);
-  ABCD_REQUIRE(ld_x >= F && ld_mu >= F && ld_lv >= F && ld_span >= D);
-  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits && span_lse));
+  ABCD_REQUIRE(ld_span >= D && (N == 0 || span_lse));
   ABCD_REQUIRE(!span_score == !span_cat);  // the best outputs come together or not at all
-  const size_t need = abcd_span_evidence_workspace_bytes(N, D, P);
-  ABCD_REQUIRE(need && ws && ws_bytes >= need);
-  if (!span_lse && !span_score) return 0;  // N = 0 with nowhere to write row 0
-  hipStream_t s = (hipStream_t)stream;
-  const long rows = std::min(N, (long)D - 1) + 1;
-  span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, span_lse, ld_span);
-  ABCD_CHECK_LAUNCH();
-  if (N == 0) return 0;
-  double* Otab = (double*)ws;
-  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<SPAN_LSE><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
-                                                    log_weight, span_score, span_cat, span_lse, ld_span, 0);
-  ABCD_CHECK_LAUNCH();
-  return 0;
+  return span_pass<SPAN_LSE>(x, ld_x, N, F, P, D, T_proto, proto_mu, ld_mu, proto_lv, ld_lv, proto_offset_logits,
+                             log_weight, span_lse, 0, span_score, span_cat, ld_span, ws, ws_bytes, stream);
 }
 
 extern "C" size_t abcd_span_viterbi_workspace_bytes(long N, int D) {
@@ -1143,15 +1162,10 @@ extern "C" int abcd_span_viterbi(const double* span_score, const int32_t* span_c
     if (V_out) ABCD_TRY(hipMemsetAsync(V_out, 0, sizeof(double), s));
     return 0;
   }
-  static bool attr = false;
-  if (!attr) {
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_viterbi, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (SP_MAX_D + 1) * (int)sizeof(double)));
-    attr = true;
-  }
-  span_viterbi<<<1, D <= SV_ONE_WAVE_D ? 64 : SV_THREADS, (size_t)D * sizeof(double), s>>>(span_score, span_cat, ld_span, N, D, d_min, gap,
-                                                                 seg_bonus, path_score, n_segments, seg_onset,
-                                                                 seg_length, seg_cat, seg_score, V_out, (int32_t*)ws);
+  ABCD_TRY(raise_lds<span_viterbi>((SP_MAX_D + 1) * sizeof(double)));
+  span_viterbi<<<1, D <= SV_ONE_WAVE_D ? 64 : SV_THREADS, (size_t)D * sizeof(double), s>>>(
+      span_score, span_cat, ld_span, N, D, d_min, gap, seg_bonus, path_score, n_segments, seg_onset, seg_length,
+      seg_cat, seg_score, V_out, (int32_t*)ws);
   ABCD_CHECK_LAUNCH();
   return 0;
 }
@@ -1171,14 +1185,8 @@ extern "C" int abcd_span_posterior(const double* span, long ld_span, long N, int
   ABCD_REQUIRE(need && ws && ws_bytes >= need);
   if (!log_z && !lattice && !post && !span_post) return 0;  // N = 0 with nowhere to write
   hipStream_t s = (hipStream_t)stream;
-  static bool attr = false;
-  if (!attr) {
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_fb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (SP_MAX_D + 1) * (int)sizeof(double)));
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_fb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (SP_MAX_D + 1) * (int)sizeof(double)));
-    attr = true;
-  }
+  ABCD_TRY(raise_lds<span_fb<true>>((SP_MAX_D + 1) * sizeof(double)));
+  ABCD_TRY(raise_lds<span_fb<false>>((SP_MAX_D + 1) * sizeof(double)));
   double* lat = lattice ? lattice : (double*)ws;
   const int threads = D <= SV_ONE_WAVE_D ? 64 : SV_THREADS;
   const size_t slots = ((size_t)D + 1) * sizeof(double);
@@ -1205,30 +1213,11 @@ extern "C" int abcd_span_table(const float* x, long ld_x, long N, int F, int P, 
                                const float* proto_offset_logits, const float* log_weight, double* table, long ld_k,
                                double* span_score, int32_t* span_cat, long ld_span, void* ws, size_t ws_bytes,
                                void* stream) {
-  ABCD_REQUIRE(span_table_ok(N, D, ld_k) && P >= 1 && F >= 1 && T_proto >= D);
-  ABCD_REQUIRE(ld_x >= F && ld_mu >= F && ld_lv >= F && ld_k >= P);
+  ABCD_REQUIRE(span_table_ok(N, D, ld_k) && ld_k >= P && (N == 0 || table));
   ABCD_REQUIRE(!span_score == !span_cat);  // the best outputs come together or not at all
   ABCD_REQUIRE(!span_score || ld_span >= D);
-  ABCD_REQUIRE(N == 0 || (x && proto_mu && proto_lv && proto_offset_logits && table));
-  const size_t need = abcd_span_table_workspace_bytes(N, D, P, ld_k);
-  ABCD_REQUIRE(need && ws && ws_bytes >= need);
-  hipStream_t s = (hipStream_t)stream;
-  const long rows = std::min(N, (long)D - 1) + 1;
-  if (table) {
-    span_table_fill<<<cdiv(rows * D * P, 256), 256, 0, s>>>(rows, D, P, table, ld_k);
-    ABCD_CHECK_LAUNCH();
-  }
-  if (span_score) {
-    span_fill<<<cdiv(rows * D, 256), 256, 0, s>>>(rows, D, span_score, span_cat, nullptr, ld_span);
-    ABCD_CHECK_LAUNCH();
-  }
-  if (N == 0) return 0;
-  double* Otab = (double*)ws;
-  span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<SPAN_TABLE><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
-                                                      log_weight, span_score, span_cat, table, ld_span, ld_k);
-  ABCD_CHECK_LAUNCH();
-  return 0;
+  return span_pass<SPAN_TABLE>(x, ld_x, N, F, P, D, T_proto, proto_mu, ld_mu, proto_lv, ld_lv, proto_offset_logits,
+                               log_weight, table, ld_k, span_score, span_cat, ld_span, ws, ws_bytes, stream);
 }
 
 extern "C" int abcd_span_chain_plan(int K, int D, int* resident, int* threads, size_t* lds_bytes) {
@@ -1266,27 +1255,14 @@ extern "C" int abcd_span_chain_viterbi(const double* table, long ld_k, long N, i
     }
     return 0;
   }
-  static bool attr = false;
-  if (!attr) {
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)span_chain_lds(SC_RES_K)));
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)std::max(span_chain_lds(SC_WIDE_K), span_chain_lds(SC_MAX_K))));
-    attr = true;
-  }
+  ABCD_TRY(raise_lds<span_chain<true>>(span_chain_lds(SC_RES_K)));
+  ABCD_TRY(raise_lds<span_chain<false>>(std::max(span_chain_lds(SC_WIDE_K), span_chain_lds(SC_MAX_K))));
   double* U = (double*)ws;
   int32_t* back_d = (int32_t*)(U + (N + 1) * K);
   int32_t* back_k = back_d + (N + 1) * K;
-  if (K <= SC_RES_K)
-    span_chain<true><<<1, 64 * span_chain_waves(K), span_chain_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, seg_bonus, log_trans,
-                                                              ld_trans, log_init, path_score, n_segments, seg_onset,
-                                                              seg_length, seg_cat, seg_score, seg_link, W_out, U,
-                                                              back_d, back_k);
-  else
-    span_chain<false><<<1, 64 * span_chain_waves(K), span_chain_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, seg_bonus, log_trans,
-                                                               ld_trans, log_init, path_score, n_segments, seg_onset,
-                                                               seg_length, seg_cat, seg_score, seg_link, W_out, U,
-                                                               back_d, back_k);
+  chain_launch(span_chain<true>, span_chain<false>, K, span_chain_lds(K), s, table, ld_k, N, D, K, d_min, gap,
+               seg_bonus, log_trans, ld_trans, log_init, path_score, n_segments, seg_onset, seg_length, seg_cat,
+               seg_score, seg_link, W_out, U, back_d, back_k);
   ABCD_CHECK_LAUNCH();
   return 0;
 }
@@ -1337,26 +1313,14 @@ extern "C" int abcd_span_chain_posterior(const double* table, long ld_k, long N,
     if (span_post) ABCD_TRY(hipMemsetAsync(span_post, 0, D * sizeof(double), s));
     return 0;
   }
-  static bool attr = false;
-  if (!attr) {
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain_fb<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)span_chain_fb_lds(SC_RES_K)));
-    ABCD_TRY(hipFuncSetAttribute((const void*)span_chain_fb<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 (int)std::max(span_chain_fb_lds(SC_WIDE_K), span_chain_fb_lds(SC_MAX_K))));
-    attr = true;
-  }
+  ABCD_TRY(raise_lds<span_chain_fb<true>>(span_chain_fb_lds(SC_RES_K)));
+  ABCD_TRY(raise_lds<span_chain_fb<false>>(std::max(span_chain_fb_lds(SC_WIDE_K), span_chain_fb_lds(SC_MAX_K))));
   double* lat = lattice ? lattice : (double*)ws;
   double* latg = lattice_g ? lattice_g : (double*)ws + 5 * (N + 1) * K;
   const double bonus = seg_bonus * scale;
-  const int threads = 64 * span_chain_waves(K);
-  if (K <= SC_RES_K)
-    span_chain_fb<true><<<1, threads, span_chain_fb_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, bonus, scale,
-                                                                  log_trans, ld_trans, log_init, log_z, lat, latg,
-                                                                  post_k, gap_post, trans_counts, init_counts);
-  else
-    span_chain_fb<false><<<1, threads, span_chain_fb_lds(K), s>>>(table, ld_k, N, D, K, d_min, gap, bonus, scale,
-                                                                   log_trans, ld_trans, log_init, log_z, lat, latg,
-                                                                   post_k, gap_post, trans_counts, init_counts);
+  chain_launch(span_chain_fb<true>, span_chain_fb<false>, K, span_chain_fb_lds(K), s, table, ld_k, N, D, K, d_min, gap,
+               bonus, scale, log_trans, ld_trans, log_init, log_z, lat, latg, post_k, gap_post, trans_counts,
+               init_counts);
   ABCD_CHECK_LAUNCH();
   if (span_post) {
     span_chain_post_table<<<cdiv((N + 1) * D, 16), 256, 0, s>>>(table, ld_k, N, D, K, d_min, bonus, scale, lat, log_z,

@@ -918,6 +918,22 @@ class RNN_Variational_Decoder(torch.nn.Module):
                                                   -1 if band is None else int(band), choice, P, F)
         return states, em, off, move
 
+    def _span_call(self, op, name, prototypes, frames, max_length, log_weight, *flags):
+        """One of the three span passes of ``ops`` on checked prototypes and frames, under ``torch.no_grad()``."""
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(frames)
+        F, D = self.rnn_cell.cell.input_size, int(max_length)
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= D >= 1):
+            raise ValueError(f"{name}: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
+        if frames.dim() != 2 or frames.shape[1] != F:
+            raise ValueError(f"{name}: frames must be N x {F}, got {tuple(frames.shape)}")
+        with torch.no_grad():
+            return op(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F), offl.reshape(-1), log_weight,
+                      int(offl.shape[1]), D, *flags)
+
     def span_scores(self, prototypes, frames, max_length, log_weight=None):
         """Every span of an uncut recording against every prototype:
         ``(span_score, span_cat)``, both ``N + 1 x max_length`` and end-major,
@@ -929,20 +945,7 @@ class RNN_Variational_Decoder(torch.nn.Module):
         that cut with a one-hot end target -- and ``span_cat`` (int32) the
         lowest p attaining it.  Entries with ``d > e`` hold -inf / -1.
         Forward-only, under ``torch.no_grad()``."""
-        mu, lv, offl = prototypes
-        N.require_gpu(mu)
-        N.require_gpu(frames)
-        F, D = self.rnn_cell.cell.input_size, int(max_length)
-        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
-                and offl.shape[0] >= D >= 1):
-            raise ValueError(f"span_scores: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
-                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
-        if frames.dim() != 2 or frames.shape[1] != F:
-            raise ValueError(f"span_scores: frames must be N x {F}, got {tuple(frames.shape)}")
-        P = int(offl.shape[1])
-        with torch.no_grad():
-            score, cat = ops.span_scores(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F), offl.reshape(-1),
-                                         log_weight, P, D)
+        score, cat = self._span_call(ops.span_scores, "span_scores", prototypes, frames, max_length, log_weight)
         return score, cat
 
     def span_evidence(self, prototypes, frames, max_length, log_weight=None, want_best=False):
@@ -954,20 +957,8 @@ class RNN_Variational_Decoder(torch.nn.Module):
         being one segment of any category.  With ``want_best`` the same pass
         also returns ``span_scores``' two tables, bit for bit; without it they
         are None.  Forward-only, under ``torch.no_grad()``."""
-        mu, lv, offl = prototypes
-        N.require_gpu(mu)
-        N.require_gpu(frames)
-        F, D = self.rnn_cell.cell.input_size, int(max_length)
-        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
-                and offl.shape[0] >= D >= 1):
-            raise ValueError(f"span_evidence: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
-                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
-        if frames.dim() != 2 or frames.shape[1] != F:
-            raise ValueError(f"span_evidence: frames must be N x {F}, got {tuple(frames.shape)}")
-        P = int(offl.shape[1])
-        with torch.no_grad():
-            lse, score, cat = ops.span_evidence(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F),
-                                                offl.reshape(-1), log_weight, P, D, bool(want_best))
+        lse, score, cat = self._span_call(ops.span_evidence, "span_evidence", prototypes, frames, max_length,
+                                          log_weight, bool(want_best))
         return (lse, score, cat) if want_best else (lse, None, None)
 
     def span_table(self, prototypes, frames, max_length, log_weight=None, want_best=False):
@@ -980,20 +971,8 @@ class RNN_Variational_Decoder(torch.nn.Module):
         (N + 1) max_length P`` bytes.  With ``want_best`` the same pass also
         returns ``span_scores``' two tables, bit for bit; without it they are
         None.  Forward-only, under ``torch.no_grad()``."""
-        mu, lv, offl = prototypes
-        N.require_gpu(mu)
-        N.require_gpu(frames)
-        F, D = self.rnn_cell.cell.input_size, int(max_length)
-        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
-                and offl.shape[0] >= D >= 1):
-            raise ValueError(f"span_table: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
-                             f"T_proto x P x {F} / T_proto x P with T_proto >= max_length = {D} >= 1")
-        if frames.dim() != 2 or frames.shape[1] != F:
-            raise ValueError(f"span_table: frames must be N x {F}, got {tuple(frames.shape)}")
-        P = int(offl.shape[1])
-        with torch.no_grad():
-            table, score, cat = ops.span_table(frames.to(mu.device), mu.reshape(-1, F), lv.reshape(-1, F),
-                                               offl.reshape(-1), log_weight, P, D, bool(want_best))
+        table, score, cat = self._span_call(ops.span_table, "span_table", prototypes, frames, max_length, log_weight,
+                                            bool(want_best))
         return (table, score, cat) if want_best else (table, None, None)
 
     def _length_to_batch_sizes(self, lengths):

@@ -849,6 +849,80 @@ _forward_only(chain_posterior, "chain_posterior")
 # ----------------------------------------------------------------------------
 # segmentation: span scores of an uncut recording and the semi-Markov programme (forward-only)
 # ----------------------------------------------------------------------------
+_TABLE_LIMIT = "D > 16383, (N + 1) * D >= 2^31 or the table's index limit (N + 1) * D * K >= 2^31"
+
+
+def _span_pass_args(name, frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D):
+    """The argument checks span_scores, span_evidence and span_table share -> the C call's inputs."""
+    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
+        N.require_gpu(t)
+    P, D = int(P), int(D)
+    if frames.dim() != 2 or frames.shape[1] < 1:
+        raise ValueError(f"{name}: frames must be N x F, got {tuple(frames.shape)}")
+    n, F = (int(v) for v in frames.shape)
+    if P < 1 or D < 1:
+        raise ValueError(f"{name}: P and D must be at least 1")
+    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
+    ol = proto_offset_logits.float().contiguous()
+    rows = int(ol.numel())
+    if rows % P or rows // P < D:
+        raise ValueError(f"{name}: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
+                         f"got {rows}")
+    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
+        raise ValueError(f"{name}: proto_mu and proto_lv must be {(rows, F)}")
+    lw = None
+    if log_weight is not None:
+        N.require_gpu(log_weight)
+        if log_weight.numel() != P:
+            raise ValueError(f"{name}: log_weight must hold {P} entries, got {log_weight.numel()}")
+        lw = log_weight.float().contiguous()
+    return n, F, P, D, x, ldx, mu, ldm, lv, ldl, ol, rows // P, lw
+
+
+def _best_tables(like, n, D, want_best):
+    """span_scores' two tables (N + 1 x D, fp64 and int32) on ``like``'s device, 0 x 0 unless wanted."""
+    shape = (n + 1, D) if want_best else (0, 0)
+    return like.new_empty(shape, dtype=torch.float64), like.new_empty(shape, dtype=torch.int32)
+
+
+def _gap_arg(name, gap, n):
+    """The N per-frame gap scores as the C call takes them (fp32, contiguous), or None."""
+    if gap is None:
+        return None
+    N.require_gpu(gap)
+    if gap.numel() != n:
+        raise ValueError(f"{name}: gap must hold {n} entries, got {gap.numel()}")
+    return gap.float().contiguous()
+
+
+def _segment_lists(cap, dev, with_link):
+    """[path_score, n_segments (0-d), onset, length, category (int32), score (, link) (fp64)], the lists max(cap,
+    1) zeros each, in the C call's order: the operators return the lists' first cap entries."""
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    return ([torch.empty((), **f64), torch.empty((), **i32)] + [torch.zeros(max(cap, 1), **i32) for _ in range(3)] +
+            [torch.zeros(max(cap, 1), **f64) for _ in range(2 if with_link else 1)])
+
+
+def _chain_args(name, table, d_min, log_trans, log_init):
+    """The argument checks span_chain_viterbi and span_chain_posterior share -> n, D, K, d_min and the C call's
+    log_trans with its row stride and log_init."""
+    for t in (table, log_trans, log_init):
+        N.require_gpu(t)
+    if table.dim() != 3 or min(table.shape) < 1:
+        raise ValueError(f"{name}: table must be N + 1 x D x K, got {tuple(table.shape)}")
+    n, D, K = int(table.shape[0]) - 1, int(table.shape[1]), int(table.shape[2])
+    d_min = int(d_min)
+    if d_min < 1 or d_min > D:
+        raise ValueError(f"{name}: d_min must lie in 1 .. {D}, got {d_min}")
+    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
+        raise ValueError(f"{name}: log_trans must be {K} x {K} and log_init hold {K} entries, got "
+                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
+    if K > 1024:
+        raise ValueError(f"{name}: at most 1024 categories, got {K}")
+    lt, ldt = _rows(log_trans.float())
+    return n, D, K, d_min, lt, ldt, log_init.float().contiguous()
+
+
 @torch.library.custom_op("abcd::span_scores", mutates_args=())
 def span_scores(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_logits: Tensor,
                 log_weight: Optional[Tensor], P: int, D: int) -> List[Tensor]:
@@ -858,46 +932,23 @@ def span_scores(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset
     ends after d frames, and that prototype (abcd_span_scores).  The prototypes
     are the time-major rectangle pairwise_nll takes, T_proto >= D; entries with
     d > e, and spans with every prototype excluded, hold -inf / -1."""
-    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
-        N.require_gpu(t)
-    P, D = int(P), int(D)
-    if frames.dim() != 2 or frames.shape[1] < 1:
-        raise ValueError(f"span_scores: frames must be N x F, got {tuple(frames.shape)}")
-    n, F = (int(v) for v in frames.shape)
-    if P < 1 or D < 1:
-        raise ValueError("span_scores: P and D must be at least 1")
-    dev = frames.device
-    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
-    ol = proto_offset_logits.float().contiguous()
-    rows = int(ol.numel())
-    if rows % P or rows // P < D:
-        raise ValueError(f"span_scores: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
-                         f"got {rows}")
-    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
-        raise ValueError(f"span_scores: proto_mu and proto_lv must be {(rows, F)}")
-    lw = None
-    if log_weight is not None:
-        N.require_gpu(log_weight)
-        if log_weight.numel() != P:
-            raise ValueError(f"span_scores: log_weight must hold {P} entries, got {log_weight.numel()}")
-        lw = log_weight.float().contiguous()
+    n, F, P, D, x, ldx, mu, ldm, lv, ldl, ol, T_proto, lw = _span_pass_args(
+        "span_scores", frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D)
     L_ = N.lib()
     nbytes = L_.abcd_span_scores_workspace_bytes(n, D, P)
     if nbytes == 0:
         raise N.HipError("span_scores: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
-    ws = N.workspace(nbytes, dev)
-    score = torch.empty(n + 1, D, dtype=torch.float64, device=dev)
-    cat = torch.empty(n + 1, D, dtype=torch.int32, device=dev)
-    N.check(L_.abcd_span_scores(N.ptr(x), ldx, n, F, P, D, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
-                                N.ptr(lw), N.ptr(score), N.ptr(cat), D, N.ptr(ws), ws.numel(), N.stream()),
+    ws = N.workspace(nbytes, frames.device)
+    score, cat = _best_tables(frames, n, D, True)
+    N.check(L_.abcd_span_scores(N.ptr(x), ldx, n, F, P, D, T_proto, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                                     N.ptr(lw), N.ptr(score), N.ptr(cat), D, N.ptr(ws), ws.numel(), N.stream()),
             "span scores")
     return [score, cat]
 
 
 @span_scores.register_fake
 def _(frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D):
-    n = frames.shape[0]
-    return [frames.new_empty(n + 1, int(D), dtype=torch.float64), frames.new_empty(n + 1, int(D), dtype=torch.int32)]
+    return list(_best_tables(frames, frames.shape[0], int(D), True))
 
 
 _forward_only(span_scores, "span_scores")
@@ -927,27 +978,19 @@ def span_viterbi(span_score: Tensor, span_cat: Tensor, d_min: int, gap: Optional
     sc, ldc = _rows(span_cat.to(torch.int32))
     if ldc != ld:  # one row stride serves both
         ss, sc, ld = ss.contiguous(), sc.contiguous(), D
-    g = None
-    if gap is not None:
-        N.require_gpu(gap)
-        if gap.numel() != n:
-            raise ValueError(f"span_viterbi: gap must hold {n} entries, got {gap.numel()}")
-        g = gap.float().contiguous()
+    g = _gap_arg("span_viterbi", gap, n)
     L_ = N.lib()
     nbytes = L_.abcd_span_viterbi_workspace_bytes(n, D)
     if nbytes == 0:
         raise N.HipError("span_viterbi: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
     ws = N.workspace(nbytes, dev)
     cap = n // d_min
-    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
-    ps, ns = torch.empty((), **f64), torch.empty((), **i32)
-    onset, length, cat = (torch.zeros(max(cap, 1), **i32) for _ in range(3))
-    score = torch.zeros(max(cap, 1), **f64)
-    V = torch.empty(n + 1 if want_v else 0, **f64)
-    N.check(L_.abcd_span_viterbi(N.ptr(ss), N.ptr(sc), ld, n, D, d_min, N.ptr(g), float(seg_bonus), N.ptr(ps),
-                                 N.ptr(ns), N.ptr(onset), N.ptr(length), N.ptr(cat), N.ptr(score),
-                                 N.ptr(V) if want_v else None, N.ptr(ws), ws.numel(), N.stream()), "span viterbi")
-    return [ps, ns, onset[:cap], length[:cap], cat[:cap], score[:cap], V]
+    outs = _segment_lists(cap, dev, False)
+    V = torch.empty(n + 1 if want_v else 0, dtype=torch.float64, device=dev)
+    N.check(L_.abcd_span_viterbi(N.ptr(ss), N.ptr(sc), ld, n, D, d_min, N.ptr(g), float(seg_bonus),
+                                 *(N.ptr(t) for t in outs), N.ptr(V) if want_v else None, N.ptr(ws), ws.numel(),
+                                 N.stream()), "span viterbi")
+    return outs[:2] + [t[:cap] for t in outs[2:]] + [V]
 
 
 @span_viterbi.register_fake
@@ -971,41 +1014,18 @@ def span_evidence(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offs
     admissible prototypes of exp(log_weight[p] - em - off) for frames e - d ..
     e - 1 (abcd_span_evidence).  With want_best the same pass also gives
     span_scores' two tables, bit for bit; without it they are 0 x 0."""
-    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
-        N.require_gpu(t)
-    P, D = int(P), int(D)
-    if frames.dim() != 2 or frames.shape[1] < 1:
-        raise ValueError(f"span_evidence: frames must be N x F, got {tuple(frames.shape)}")
-    n, F = (int(v) for v in frames.shape)
-    if P < 1 or D < 1:
-        raise ValueError("span_evidence: P and D must be at least 1")
-    dev = frames.device
-    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
-    ol = proto_offset_logits.float().contiguous()
-    rows = int(ol.numel())
-    if rows % P or rows // P < D:
-        raise ValueError(f"span_evidence: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
-                         f"got {rows}")
-    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
-        raise ValueError(f"span_evidence: proto_mu and proto_lv must be {(rows, F)}")
-    lw = None
-    if log_weight is not None:
-        N.require_gpu(log_weight)
-        if log_weight.numel() != P:
-            raise ValueError(f"span_evidence: log_weight must hold {P} entries, got {log_weight.numel()}")
-        lw = log_weight.float().contiguous()
+    n, F, P, D, x, ldx, mu, ldm, lv, ldl, ol, T_proto, lw = _span_pass_args(
+        "span_evidence", frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D)
     L_ = N.lib()
     nbytes = L_.abcd_span_evidence_workspace_bytes(n, D, P)
     if nbytes == 0:
         raise N.HipError("span_evidence: unsupported shape (D > 16383 or (N + 1) * D >= 2^31)")
-    ws = N.workspace(nbytes, dev)
-    lse = torch.empty(n + 1, D, dtype=torch.float64, device=dev)
-    shape = (n + 1, D) if want_best else (0, 0)
-    score = torch.empty(shape, dtype=torch.float64, device=dev)
-    cat = torch.empty(shape, dtype=torch.int32, device=dev)
-    N.check(L_.abcd_span_evidence(N.ptr(x), ldx, n, F, P, D, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
-                                  N.ptr(lw), N.ptr(lse), N.ptr(score) if want_best else None,
-                                  N.ptr(cat) if want_best else None, D, N.ptr(ws), ws.numel(), N.stream()),
+    ws = N.workspace(nbytes, frames.device)
+    lse = torch.empty(n + 1, D, dtype=torch.float64, device=frames.device)
+    score, cat = _best_tables(frames, n, D, want_best)
+    N.check(L_.abcd_span_evidence(N.ptr(x), ldx, n, F, P, D, T_proto, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                                       N.ptr(lw), N.ptr(lse), N.ptr(score) if want_best else None,
+                                       N.ptr(cat) if want_best else None, D, N.ptr(ws), ws.numel(), N.stream()),
             "span evidence")
     return [lse, score, cat]
 
@@ -1013,9 +1033,7 @@ def span_evidence(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offs
 @span_evidence.register_fake
 def _(frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D, want_best):
     n = frames.shape[0]
-    shape = (n + 1, int(D)) if want_best else (0, 0)
-    return [frames.new_empty(n + 1, int(D), dtype=torch.float64), frames.new_empty(shape, dtype=torch.float64),
-            frames.new_empty(shape, dtype=torch.int32)]
+    return [frames.new_empty(n + 1, int(D), dtype=torch.float64), *_best_tables(frames, n, int(D), want_best)]
 
 
 _forward_only(span_evidence, "span_evidence")
@@ -1039,12 +1057,7 @@ def span_posterior(span: Tensor, d_min: int, gap: Optional[Tensor], seg_bonus: f
         raise ValueError(f"span_posterior: d_min must lie in 1 .. {D}, got {d_min}")
     dev = span.device
     ss, ld = _rows(span.double())
-    g = None
-    if gap is not None:
-        N.require_gpu(gap)
-        if gap.numel() != n:
-            raise ValueError(f"span_posterior: gap must hold {n} entries, got {gap.numel()}")
-        g = gap.float().contiguous()
+    g = _gap_arg("span_posterior", gap, n)
     L_ = N.lib()
     nbytes = L_.abcd_span_posterior_workspace_bytes(n, D)
     if nbytes == 0:
@@ -1071,9 +1084,6 @@ def _(span, d_min, gap, seg_bonus, want_table):
 _forward_only(span_posterior, "span_posterior")
 
 
-_TABLE_LIMIT = "D > 16383, (N + 1) * D >= 2^31 or the table's index limit (N + 1) * D * K >= 2^31"
-
-
 @torch.library.custom_op("abcd::span_table", mutates_args=())
 def span_table(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_logits: Tensor,
                log_weight: Optional[Tensor], P: int, D: int, want_best: bool) -> List[Tensor]:
@@ -1083,41 +1093,18 @@ def span_table(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_
     frames (abcd_span_table); excluded prototypes and entries with d > e hold
     -inf.  With want_best the same pass also gives span_scores' two tables, bit
     for bit; without it they are 0 x 0."""
-    for t in (frames, proto_mu, proto_lv, proto_offset_logits):
-        N.require_gpu(t)
-    P, D = int(P), int(D)
-    if frames.dim() != 2 or frames.shape[1] < 1:
-        raise ValueError(f"span_table: frames must be N x F, got {tuple(frames.shape)}")
-    n, F = (int(v) for v in frames.shape)
-    if P < 1 or D < 1:
-        raise ValueError("span_table: P and D must be at least 1")
-    dev = frames.device
-    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
-    ol = proto_offset_logits.float().contiguous()
-    rows = int(ol.numel())
-    if rows % P or rows // P < D:
-        raise ValueError(f"span_table: the prototype rectangle must hold T_proto * {P} rows with T_proto >= {D}, "
-                         f"got {rows}")
-    if not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
-        raise ValueError(f"span_table: proto_mu and proto_lv must be {(rows, F)}")
-    lw = None
-    if log_weight is not None:
-        N.require_gpu(log_weight)
-        if log_weight.numel() != P:
-            raise ValueError(f"span_table: log_weight must hold {P} entries, got {log_weight.numel()}")
-        lw = log_weight.float().contiguous()
+    n, F, P, D, x, ldx, mu, ldm, lv, ldl, ol, T_proto, lw = _span_pass_args(
+        "span_table", frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D)
     L_ = N.lib()
     nbytes = L_.abcd_span_table_workspace_bytes(n, D, P, P)
     if nbytes == 0:
         raise N.HipError(f"span_table: unsupported shape ({_TABLE_LIMIT}); N = {n}, D = {D}, K = {P}")
-    ws = N.workspace(nbytes, dev)
-    table = torch.empty(n + 1, D, P, dtype=torch.float64, device=dev)
-    shape = (n + 1, D) if want_best else (0, 0)
-    score = torch.empty(shape, dtype=torch.float64, device=dev)
-    cat = torch.empty(shape, dtype=torch.int32, device=dev)
-    N.check(L_.abcd_span_table(N.ptr(x), ldx, n, F, P, D, rows // P, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
-                               N.ptr(lw), N.ptr(table), P, N.ptr(score) if want_best else None,
-                               N.ptr(cat) if want_best else None, D, N.ptr(ws), ws.numel(), N.stream()),
+    ws = N.workspace(nbytes, frames.device)
+    table = torch.empty(n + 1, D, P, dtype=torch.float64, device=frames.device)
+    score, cat = _best_tables(frames, n, D, want_best)
+    N.check(L_.abcd_span_table(N.ptr(x), ldx, n, F, P, D, T_proto, N.ptr(mu), ldm, N.ptr(lv), ldl, N.ptr(ol),
+                                    N.ptr(lw), N.ptr(table), P, N.ptr(score) if want_best else None,
+                                    N.ptr(cat) if want_best else None, D, N.ptr(ws), ws.numel(), N.stream()),
             "span table")
     return [table, score, cat]
 
@@ -1125,9 +1112,7 @@ def span_table(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, proto_offset_
 @span_table.register_fake
 def _(frames, proto_mu, proto_lv, proto_offset_logits, log_weight, P, D, want_best):
     n = frames.shape[0]
-    shape = (n + 1, int(D)) if want_best else (0, 0)
-    return [frames.new_empty(n + 1, int(D), int(P), dtype=torch.float64),
-            frames.new_empty(shape, dtype=torch.float64), frames.new_empty(shape, dtype=torch.int32)]
+    return [frames.new_empty(n + 1, int(D), int(P), dtype=torch.float64), *_best_tables(frames, n, int(D), want_best)]
 
 
 _forward_only(span_table, "span_table")
@@ -1144,45 +1129,22 @@ def span_chain_viterbi(table: Tensor, d_min: int, gap: Optional[Tensor], seg_bon
     a copy) paid between consecutive segments and log_init[k] on the first
     (abcd_span_chain_viterbi).  link is that term per segment.  Only the first
     n_segments entries of the segment lists are written."""
-    for t in (table, log_trans, log_init):
-        N.require_gpu(t)
-    if table.dim() != 3 or min(table.shape) < 1:
-        raise ValueError(f"span_chain_viterbi: table must be N + 1 x D x K, got {tuple(table.shape)}")
-    n, D, K = int(table.shape[0]) - 1, int(table.shape[1]), int(table.shape[2])
-    d_min = int(d_min)
-    if d_min < 1 or d_min > D:
-        raise ValueError(f"span_chain_viterbi: d_min must lie in 1 .. {D}, got {d_min}")
-    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
-        raise ValueError(f"span_chain_viterbi: log_trans must be {K} x {K} and log_init hold {K} entries, got "
-                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
-    if K > 1024:
-        raise ValueError(f"span_chain_viterbi: at most 1024 categories, got {K}")
+    n, D, K, d_min, lt, ldt, li = _chain_args("span_chain_viterbi", table, d_min, log_trans, log_init)
     dev = table.device
     tb = table.double().contiguous()
-    lt, ldt = _rows(log_trans.float())
-    li = log_init.float().contiguous()
-    g = None
-    if gap is not None:
-        N.require_gpu(gap)
-        if gap.numel() != n:
-            raise ValueError(f"span_chain_viterbi: gap must hold {n} entries, got {gap.numel()}")
-        g = gap.float().contiguous()
+    g = _gap_arg("span_chain_viterbi", gap, n)
     L_ = N.lib()
     nbytes = L_.abcd_span_chain_workspace_bytes(n, D, K)
     if nbytes == 0:
         raise N.HipError(f"span_chain_viterbi: unsupported shape ({_TABLE_LIMIT}); N = {n}, D = {D}, K = {K}")
     ws = N.workspace(nbytes, dev)
     cap = n // d_min
-    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
-    ps, ns = torch.empty((), **f64), torch.empty((), **i32)
-    onset, length, cat = (torch.zeros(max(cap, 1), **i32) for _ in range(3))
-    score, link = torch.zeros(max(cap, 1), **f64), torch.zeros(max(cap, 1), **f64)
-    W = torch.empty((n + 1, K) if want_w else (0, K), **f64)
+    outs = _segment_lists(cap, dev, True)
+    W = torch.empty((n + 1, K) if want_w else (0, K), dtype=torch.float64, device=dev)
     N.check(L_.abcd_span_chain_viterbi(N.ptr(tb), K, n, D, K, d_min, N.ptr(g), float(seg_bonus), N.ptr(lt), ldt,
-                                       N.ptr(li), N.ptr(ps), N.ptr(ns), N.ptr(onset), N.ptr(length), N.ptr(cat),
-                                       N.ptr(score), N.ptr(link), N.ptr(W) if want_w else None, N.ptr(ws),
+                                       N.ptr(li), *(N.ptr(t) for t in outs), N.ptr(W) if want_w else None, N.ptr(ws),
                                        ws.numel(), N.stream()), "span chain viterbi")
-    return [ps, ns, onset[:cap], length[:cap], cat[:cap], score[:cap], link[:cap], W]
+    return outs[:2] + [t[:cap] for t in outs[2:]] + [W]
 
 
 @span_chain_viterbi.register_fake
@@ -1210,35 +1172,17 @@ def span_chain_posterior(table: Tensor, d_min: int, gap: Optional[Tensor], seg_b
     temperature) in fp64 (abcd_span_chain_posterior).  The counts and
     span_post are empty tensors unless asked for.  An uncoverable recording
     gives log_z = -inf and zeros."""
-    for t in (table, log_trans, log_init):
-        N.require_gpu(t)
-    if table.dim() != 3 or min(table.shape) < 1:
-        raise ValueError(f"span_chain_posterior: table must be N + 1 x D x K, got {tuple(table.shape)}")
-    n, D, K = int(table.shape[0]) - 1, int(table.shape[1]), int(table.shape[2])
-    d_min, scale = int(d_min), float(scale)
-    if d_min < 1 or d_min > D:
-        raise ValueError(f"span_chain_posterior: d_min must lie in 1 .. {D}, got {d_min}")
+    scale = float(scale)
     if not (scale > 0.0 and math.isfinite(scale)):
         raise ValueError(f"span_chain_posterior: scale must be positive and finite, got {scale}")
-    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
-        raise ValueError(f"span_chain_posterior: log_trans must be {K} x {K} and log_init hold {K} entries, got "
-                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
-    if K > 1024:
-        raise ValueError(f"span_chain_posterior: at most 1024 categories, got {K}")
+    n, D, K, d_min, lt, ldt, li = _chain_args("span_chain_posterior", table, d_min, log_trans, log_init)
     L_ = N.lib()
     nbytes = L_.abcd_span_chain_posterior_workspace_bytes(n, D, K)
     if nbytes == 0:
         raise N.HipError(f"span_chain_posterior: unsupported shape ({_TABLE_LIMIT}); N = {n}, D = {D}, K = {K}")
     dev = table.device
     tb = table.double().contiguous()
-    lt, ldt = _rows(log_trans.float())
-    li = log_init.float().contiguous()
-    g = None
-    if gap is not None:
-        N.require_gpu(gap)
-        if gap.numel() != n:
-            raise ValueError(f"span_chain_posterior: gap must hold {n} entries, got {gap.numel()}")
-        g = gap.float().contiguous()
+    g = _gap_arg("span_chain_posterior", gap, n)
     ws = N.workspace(nbytes, dev)
     f64 = dict(dtype=torch.float64, device=dev)
     log_z = torch.empty((), **f64)

@@ -95,8 +95,9 @@ def segment_frames(decoder, prototypes, frames, max_length, min_length=1, log_we
     return out
 
 
-def _chain_of(transitions, device):
-    """(log_trans K x K, log_init K) fp32 on ``device`` from a TransitionModel or a pair."""
+def _chain_setup(name, transitions, prototypes, device):
+    """(log_trans K x K, log_init K, K) from a TransitionModel or a pair, fp32 on
+    ``device``, K being the prototypes' category count (``name``: the caller, for the message)."""
     if hasattr(transitions, "log_trans") and hasattr(transitions, "log_init"):
         lt, li = transitions.log_trans, transitions.log_init
     else:
@@ -106,15 +107,15 @@ def _chain_of(transitions, device):
     if lt.dim() != 2 or lt.shape[0] != lt.shape[1] or li.numel() != lt.shape[0]:
         raise ValueError(f"transitions: log_trans must be K x K and log_init hold K entries, got {tuple(lt.shape)} "
                          f"and {tuple(li.shape)}")
-    return lt, li
+    K = int(prototypes[2].shape[1])
+    if lt.shape[0] != K:
+        raise ValueError(f"{name}: the transition model has {lt.shape[0]} categories, the prototypes {K}")
+    return lt, li, K
 
 
 def _segment_chain(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions, include_weight):
     """segment_frames under a transition model (see there)."""
-    lt, li = _chain_of(transitions, frames.device)
-    K = int(prototypes[2].shape[1])
-    if lt.shape[0] != K:
-        raise ValueError(f"segment_frames: the transition model has {lt.shape[0]} categories, the prototypes {K}")
+    lt, li, K = _chain_setup("segment_frames", transitions, prototypes, frames.device)
     lw = None if log_weight is None else torch.as_tensor(log_weight, device=frames.device).float().reshape(-1)
     with torch.no_grad():
         table, _, _ = decoder.span_table(prototypes, frames, D, log_weight=lw if include_weight else None)
@@ -227,11 +228,7 @@ def segment_chain_posteriors(decoder, prototypes, frames, max_length, transition
         raise ValueError(f"segment_chain_posteriors: 1 <= min_length <= max_length, got {d_min} and {D}")
     if not (T > 0.0 and math.isfinite(T)):
         raise ValueError(f"temperature must be positive, got {temperature}")
-    lt, li = _chain_of(transitions, frames.device)
-    K = int(prototypes[2].shape[1])
-    if lt.shape[0] != K:
-        raise ValueError(f"segment_chain_posteriors: the transition model has {lt.shape[0]} categories, the "
-                         f"prototypes {K}")
+    lt, li, K = _chain_setup("segment_chain_posteriors", transitions, prototypes, frames.device)
     lw = None if log_weight is None else torch.as_tensor(log_weight, device=frames.device).float().reshape(-1)
     s = 1.0 / T
     with torch.no_grad():

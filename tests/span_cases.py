@@ -231,6 +231,49 @@ def table_inputs(N, D, kind):
 
 
 # ----------------------------------------------------------------------------
+# candidate lengths past the registers
+# ----------------------------------------------------------------------------
+TAIL_FROM = 1025
+"""The shortest candidate that the dynamic programmes take from their loop and
+not from a register: four waves hold four candidates per thread, d <= 1024."""
+TAIL_CASES = dict(forced=(2055, 1030, 1025), mixed=(1100, 1030, 1))
+"""(N, D, d_min).  forced: without a gap the only covers are the six pairs
+(1025, 1030) .. (1030, 1025), so every candidate of every step comes from the
+loop.  mixed: columns d >= TAIL_FROM carry TAIL_REWARD, so both kinds of
+candidate compete in one step."""
+TAIL_REWARD = 2200.0
+"""The best cover by segments of at most 1024 frames scores 1973 over the 1100
+frames on these N(0, 3) entries without a gap and 2047 with one (the float64
+loop), and the sum over such covers lies some tens above the best of them: at
+2000 the best path already holds a long segment while its posterior is 5e-15.
+At 2200 the best path holds one long segment with short ones around it and the
+posterior agrees (test_span_cpu.py and test_spanpost_cpu.py assert both)."""
+
+
+@functools.lru_cache(maxsize=None)
+def tail_inputs(name):
+    """table_inputs("random") at TAIL_CASES[name]: dict(score, cat, gap, N, D, d_min).  Shared, never modified."""
+    N, D, d_min = TAIL_CASES[name]
+    g = np.random.default_rng(7919 * N + 31 * D + d_min)
+    ss = g.normal(0.0, 3.0, size=(N + 1, D))
+    if name == "mixed":
+        ss[:, TAIL_FROM - 1:] += TAIL_REWARD
+    cat = g.integers(0, 5, size=(N + 1, D)).astype(np.int32)
+    late = np.arange(D)[None, :] >= np.arange(N + 1)[:, None]   # d > e
+    ss[late] = NEG
+    cat[late] = -1
+    gap = g.normal(-1.0, 1.0, size=N).astype(np.float32)
+    return dict(score=ss, cat=cat, gap=gap, N=N, D=D, d_min=d_min)
+
+
+@functools.lru_cache(maxsize=None)
+def tail_viterbi(name, with_gap):
+    """viterbi_reference on tail_inputs(name), bonus 0.  Shared, never modified."""
+    t = tail_inputs(name)
+    return viterbi_reference(t["score"], t["cat"], t["d_min"], t["gap"] if with_gap else None, 0.0)
+
+
+# ----------------------------------------------------------------------------
 # the planted case
 # ----------------------------------------------------------------------------
 PLANT_F, PLANT_P, PLANT_D = 33, 5, 12

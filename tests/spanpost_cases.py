@@ -245,6 +245,13 @@ def evidence_case(N, D, P, F):
     return dict(c, lse=lse_reference(c["ref"]["S"]), unit=unit_reference(c["ref"]["S"], c["ref"]["A"]))
 
 
+@functools.lru_cache(maxsize=None)
+def tail_posterior(name, with_gap):
+    """posterior_reference_fast on span_cases.tail_inputs(name), bonus 0 (shared, never modified)."""
+    t = SP.tail_inputs(name)
+    return posterior_reference_fast(t["score"], t["d_min"], t["gap"] if with_gap else None, 0.0)
+
+
 def dump(name, rows):
     """The figures a GPU test observed (ABCD_PARITY_DUMP=<dir>, as edge_cases.dump_observed)."""
     PW.E.dump_observed("spanpost_" + name, rows)

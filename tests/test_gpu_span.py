@@ -226,6 +226,17 @@ def test_span_viterbi_is_the_float64_loop(N, D):
     assert reached > 0
 
 
+@pytest.mark.parametrize("with_gap", (False, True), ids=("nogap", "gap"))
+@pytest.mark.parametrize("name", list(SP.TAIL_CASES))
+def test_span_viterbi_past_the_register_candidates(name, with_gap):
+    """Candidate lengths above 1024 come from the step's loop, not from the
+    four registers per thread (span_cases.TAIL_CASES; the conditions on the
+    reference are asserted in test_span_cpu.py): equality with the float64 loop."""
+    t = SP.tail_inputs(name)
+    ref = _check_viterbi(t["score"], t["cat"], t["d_min"], t["gap"] if with_gap else None, 0.0, (name, with_gap))
+    assert ref["path_score"] > NEG and max(ref["length"]) >= SP.TAIL_FROM
+
+
 def test_span_viterbi_on_the_span_kernel_output():
     """The programme on abcd_span_scores' own (row-strided) output through the C
     ABI, with and without V_out: equal to the loop on the same table."""

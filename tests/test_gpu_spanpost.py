@@ -276,6 +276,20 @@ def test_span_posterior_at_the_ring_threshold(D):
     assert reached >= 8
 
 
+@pytest.mark.parametrize("with_gap", (False, True), ids=("nogap", "gap"))
+@pytest.mark.parametrize("name", list(SP.TAIL_CASES))
+def test_span_posterior_past_the_register_candidates(name, with_gap):
+    """Candidate lengths above 1024 come from the loops of the forward sweep's
+    two passes and of the backward fold (span_cases.TAIL_CASES; the conditions
+    on the reference are asserted in test_spanpost_cpu.py)."""
+    t = SP.tail_inputs(name)
+    gap = t["gap"] if with_gap else None
+    got = posterior_call(t["score"], t["d_min"], gap, 0.0)
+    e = check_posterior(got, SQ.tail_posterior(name, with_gap), t["N"], t["D"], with_gap, (name, with_gap))
+    print(f"{name} gap={with_gap}: lattice error {e[0]:.2e} of its bar, posteriors {e[1]:.2e}, identities and "
+          f"beta[0] {e[2]:.2e} of theirs")
+
+
 # ----------------------------------------------------------------------------
 # 5 / 6. the programme on the span kernel's own output; the order of the three quantities
 # ----------------------------------------------------------------------------

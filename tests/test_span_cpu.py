@@ -355,3 +355,20 @@ def test_frames_to_seconds_round_trip_through_the_loader(tmp_path, centering):
         assert (off[:-1] < on[1:]).all()
     mask = segment.covered_frames(n, on[:1], off[:1], fs, frame, hop, centering)
     assert mask[:d0].all() and not mask[d0 + (0 if centering else 2):].any()
+
+
+@pytest.mark.parametrize("with_gap", (False, True), ids=("nogap", "gap"))
+def test_tail_cases_reach_past_the_register_candidates(with_gap):
+    """The conditions of span_cases.TAIL_CASES on the float64 loop alone: the
+    forced case has a cover and every segment of it is a loop candidate; the
+    mixed case's best path holds segments of both kinds."""
+    forced, mixed = SP.tail_viterbi("forced", with_gap), SP.tail_viterbi("mixed", with_gap)
+    N, D, d_min = SP.TAIL_CASES["forced"]
+    assert d_min >= SP.TAIL_FROM and 2 * d_min <= N <= 2 * D
+    if not with_gap:                                # nothing but the six pairs (1025, 1030) .. (1030, 1025)
+        assert sum(1 for a in range(d_min, D + 1) if d_min <= N - a <= D) == 6 and N < 3 * d_min
+        assert len(forced["length"]) == 2 and sum(forced["length"]) == N
+    assert forced["path_score"] > NEG and forced["length"] and min(forced["length"]) >= SP.TAIL_FROM
+    lengths = np.array(mixed["length"])
+    print(f"mixed: {(lengths >= SP.TAIL_FROM).sum()} long and {(lengths < SP.TAIL_FROM).sum()} short segments")
+    assert (lengths >= SP.TAIL_FROM).any() and (lengths < SP.TAIL_FROM).any()

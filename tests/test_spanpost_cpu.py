@@ -303,3 +303,16 @@ def test_segment_rows_and_writer_carry_the_posterior_columns(tmp_path):
     with np.load(cur) as z:
         assert z["onset"].shape == (14,) and float(z["log_evidence"]) == -2.5 and int(z["hop"]) == 32
     assert not [f for f in os.listdir(str(tmp_path)) if f.endswith(".partial")]
+
+
+@pytest.mark.parametrize("with_gap", (False, True), ids=("nogap", "gap"))
+def test_tail_cases_keep_mass_on_both_kinds_of_candidate(with_gap):
+    """The conditions of span_cases.TAIL_CASES on the reference alone: the forced
+    case can be covered, all of its mass on loop candidates; the mixed case's
+    span posterior has at least 1e-3 on either side of the registers' reach."""
+    cut = SP.TAIL_FROM - 1
+    forced = SQ.tail_posterior("forced", with_gap)
+    assert forced["log_z"] > NEG and forced["span_post"][:, cut:].sum() >= 1e-3 and not forced["span_post"][:, :cut].any()
+    mixed = SQ.tail_posterior("mixed", with_gap)["span_post"]
+    print(f"mixed: mass {mixed[:, cut:].sum():.3g} on d >= {SP.TAIL_FROM}, {mixed[:, :cut].sum():.3g} below")
+    assert mixed[:, cut:].sum() >= 1e-3 and mixed[:, :cut].sum() >= 1e-3
