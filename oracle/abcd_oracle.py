@@ -200,9 +200,12 @@ def rnn_layer_packed(x, batch_sizes, w, rnn, reverse):
     return out, fh, fc
 
 
-def encoder_forward(P, data, batch_sizes, cfg):
+def encoder_forward(P, data, batch_sizes, cfg, hmask=None):
     """model.py:60-66: returns last_hidden (B x hidden_size_total) laid out as
-    transpose(cat(h_n, c_n, -1), 0, 1).view(B, -1)."""
+    transpose(cat(h_n, c_n, -1), 0, 1).view(B, -1).  hmask: training-mode
+    inter-layer dropout noise (model.py:53, nn.LSTM/GRU's dropout), one
+    L x dirs*H tensor bernoulli(1-p)/(1-p) per layer boundary: layer l + 1
+    reads x * hmask[l]."""
     dirs = ["", "_reverse"] if cfg["bidirectional"] else [""]
     x = data
     pieces = []
@@ -214,6 +217,8 @@ def encoder_forward(P, data, batch_sizes, cfg):
             outs.append(out)
             pieces.append(torch.cat([fh, fc], -1) if cfg["rnn"] == "LSTM" else fh)
         x = torch.cat(outs, -1)
+        if hmask is not None and l + 1 < cfg["layers"]:
+            x = x * hmask[l]
     return torch.cat(pieces, -1)
 
 

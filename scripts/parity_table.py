@@ -4,7 +4,7 @@
     ABCD_PARITY_DUMP=<dir> python -m pytest -m gpu tests
     python scripts/parity_table.py <dir>
 
-tests/test_gpu_edges.py, test_gpu_ladder.py, test_gpu_fullshape.py,
+tests/test_gpu_edges.py, test_gpu_ladder.py, test_gpu_decoder_noise.py, test_gpu_fullshape.py,
 test_gpu_prod.py, test_gpu_sampler_widths.py and test_gpu_philox.py write the errors they
 observed (the HIP path against the float64 / fp32 oracle or the reference's
 fixtures) into <dir> when ABCD_PARITY_DUMP is set; this puts them into one
@@ -28,6 +28,7 @@ def sig(x, n=3):
 
 def main(src):
     import edge_cases as E
+    import test_gpu_decoder_noise as TN
     import test_gpu_edges as TE
     import test_gpu_fullshape as TF
     import test_gpu_ladder as TL
@@ -35,6 +36,7 @@ def main(src):
     import test_gpu_sampler_widths as TS
     edges, full, prod, samp, philox, ladder = {}, {}, {}, {}, {}, {}
     worst_ratio, samp_ratio, ladder_ratio = {}, {}, {}
+    noise, noise_ratio = {}, {}
     for path in sorted(glob.glob(os.path.join(src, "*.json"))):
         name = os.path.basename(path)[:-5]
         with open(path) as f:
@@ -62,6 +64,17 @@ def main(src):
                         if sig(a / max(b, 1e-30)) > ladder_ratio.get(key, (0.0, ""))[0]:
                             ladder_ratio[key] = (sig(a / max(b, 1e-30)), name[len("ladder-"):])
             ladder[name[len("ladder-"):]] = rows
+        elif name.startswith("noise-"):
+            rows = {}
+            for r in d:
+                k = r["tensor"]
+                rows[k] = [sig(r["e32_rel"]), sig(r["e_hip_rel"]), sig(r["e32_blk"]), sig(r["e_hip_blk"]), r["R"]]
+                for a, b in ((r["e_hip_rel"], r["e32_rel"]), (r["e_hip_blk"], r["e32_blk"])):
+                    if a > TL.bound(TL.R_DEFAULT, b):  # past the default bound
+                        key = ("encoder: " if name.startswith("noise-encdrop-") else "") + k
+                        if sig(a / max(b, 1e-30)) > noise_ratio.get(key, (0.0, ""))[0]:
+                            noise_ratio[key] = (sig(a / max(b, 1e-30)), name[len("noise-"):])
+            noise[name[len("noise-"):]] = rows
         elif name.startswith("philox-"):
             philox[name[len("philox-"):]] = {k: (sig(v) if isinstance(v, float) else v) for k, v in d[0].items()}
         elif name.startswith("fullshape-"):
@@ -112,6 +125,24 @@ def main(src):
                             for m, i in (("rel", 1), ("blk", 3))} if ladder else {},
             "cases": ladder,
         },
+        "decoder_noise": {
+            "file": "tests/test_gpu_decoder_noise.py (cases, masks, streams and references: tests/noise_cases.py)",
+            "reference": "mask-* / maskframes-*: the float64 oracle step fed the replayed input-dropout mask; philox-*: "
+                         "the float64 oracle step fed abcd_fill_normal / abcd_fill_dropout's values of the step's "
+                         "(seed, offset); encdrop-*: oracle.encoder_forward(hmask=...) with autograd in float64; e32 "
+                         "the same in fp32",
+            "columns": ["e32_rel", "e_hip_rel", "e32_blk", "e_hip_blk", "R"],
+            "bound": "e_hip <= R * e32 + 1e-7, and e_hip <= %g whatever R" % TL.HARD,
+            "R_default": TL.R_DEFAULT,
+            "R_imported": "test_gpu_edges.R_TENSOR (rung1), test_gpu_ladder.R_TENSOR (the other rows) and "
+                          "test_gpu_ladder.R_ENCODER (encdrop), unchanged",
+            "R_step": TN.R_STEP, "R_enc": TN.R_ENC,
+            "worst_ratio_past_R_default": {k: list(v) for k, v in sorted(noise_ratio.items())},
+            "R_note": "R is raised only for a tensor past its bound here, to at most 2 x its own worst ratio. " + TN.R_NOTE,
+            "worst_e_hip": {m: max(r[i] for rows in noise.values() for r in rows.values())
+                            for m, i in (("rel", 1), ("blk", 3))} if noise else {},
+            "cases": noise,
+        },
         "full_shape": {
             "file": "tests/test_gpu_fullshape.py", "reference": "the fp32 oracle (oracle.train_step)",
             "metrics": "rel / blk / norm: a gradient against the oracle's; sgd: the post-SGD delta less the stored "
@@ -152,7 +183,7 @@ def main(src):
     if os.path.isfile(out):
         with open(out) as f:
             old = json.load(f)
-        for sec, got in (("edge_cases", edges), ("ladder", ladder), ("full_shape", full), ("prod_fixtures", prod),
+        for sec, got in (("edge_cases", edges), ("ladder", ladder), ("decoder_noise", noise), ("full_shape", full), ("prod_fixtures", prod),
                          ("sampler_widths", samp or philox)):
             if not got and sec in old:
                 table[sec] = old[sec]
