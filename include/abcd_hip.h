@@ -756,6 +756,45 @@ int abcd_span_posterior(const double* span, long ld_span, long N, int D, int d_m
  * abcd_span_chain_viterbi 209 ms (14 us per step; 19 us at K = 130, streaming):
  * the step is bound by reading its 205 KB table row on one CU.
  *
+ * abcd_span_chain_viterbi_window: abcd_span_chain_viterbi in windows of ends
+ * (DESIGN.md s3.15), for recordings whose whole table does not fit.  One call
+ * runs steps n0 .. n1 of the recurrences above on a WINDOW of the table: row 0
+ * of `table` is absolute end row0 and the buffer holds `rows` rows,
+ *   step n reads table[((n - row0) D + d - 1) ld_k + k],  d_min <= d <= min(D, n)
+ * (rows n0 - row0 .. n1 - row0 and no others).  abcd_span_table on the frames
+ * row0 .. n1 - 1 (x + row0 ld_x, N = n1 - row0) IS that window when row0 is a
+ * multiple of 32, the table pass's start tile: every start then sits at the
+ * same place of its tile as in the pass over the whole recording, and every
+ * entry with end >= n0 has the same bits.  The caller guarantees row0 <=
+ * max(0, n0 - D), so every entry read is a real one.
+ * Call order: n0 = 1 first, then every call's n0 = the previous call's n1 + 1,
+ * until n1 = N; all calls of one recording on ONE stream (or otherwise
+ * ordered) with the same workspace, N, D, K, d_min, seg_bonus, log_trans,
+ * log_init, gap and W_out.  gap (N floats or NULL) and W_out ((N + 1) x K
+ * doubles or NULL) are whole-recording buffers; each call reads gap[n0 - 1 ..
+ * n1 - 1] and writes rows n0 .. n1 of W_out (row 0 too when n0 = 1).
+ * path_score, n_segments and the five segment buffers are written by the call
+ * with n1 = N alone, with the bits abcd_span_chain_viterbi writes on the whole
+ * table.  The workspace carries the programme across the calls and must not
+ * be touched between them: U and sel (the chosen segment's table entry per
+ * (n, k): the table is gone when the backtrack runs), (N + 1) K doubles each,
+ * the two back-pointer planes ((N + 1) K int32 each), and the carry block W[n1]
+ * (K doubles), G[n1] and next_n = n1 + 1 (one 64-bit integer).  A call with n0
+ * = 1 starts over on whatever the workspace holds.  A call whose n0 is neither
+ * 1 nor the carried next_n is a caller's mistake: it runs no step, writes
+ * path_score = NaN and n_segments = -1 and leaves the carry as it is.
+ * Launch widths, LDS plan, tie rules: abcd_span_chain_plan; log_init and the
+ * resident log_trans are loaded into LDS by every call.  No atomics, no
+ * device-global word; two sequences of calls agree bit for bit.
+ * Limits: 1 <= K <= 1024, span_scores' on (N, D); rows D ld_k < 2^31 (the
+ * window's index limit; (N + 1) D K is NOT limited).  The workspace query
+ * returns 0 beyond them.  ABCD_EINVAL (on the host before any launch, nothing
+ * is written): those limits, not 1 <= n0 <= n1 <= N (N = 0 among them: take
+ * abcd_span_chain_viterbi), row0 < 0, row0 > max(0, n0 - D), n1 - row0 >= rows,
+ * d_min outside 1 .. D, ld_k < K, ld_trans < K, a NULL among table, log_trans,
+ * log_init, path_score, n_segments and the five segment buffers, a missing or
+ * short workspace.
+ *
  * No timing or dispatch id is assigned to these entry points.
  * ---------------------------------------------------------------------- */
 size_t abcd_span_table_workspace_bytes(long N, int D, int P, long ld_k);
@@ -770,6 +809,13 @@ int abcd_span_chain_viterbi(const double* table, long ld_k, long N, int D, int K
                             double* path_score, int32_t* n_segments, int32_t* seg_onset, int32_t* seg_length,
                             int32_t* seg_cat, double* seg_score, double* seg_link, double* W_out, void* ws,
                             size_t ws_bytes, void* stream);
+size_t abcd_span_chain_window_workspace_bytes(long N, int D, int K);
+int abcd_span_chain_viterbi_window(const double* table, long ld_k, long row0, long rows, long n0, long n1, long N,
+                                   int D, int K, int d_min, const float* gap, double seg_bonus,
+                                   const float* log_trans, long ld_trans, const float* log_init, double* path_score,
+                                   int32_t* n_segments, int32_t* seg_onset, int32_t* seg_length, int32_t* seg_cat,
+                                   double* seg_score, double* seg_link, double* W_out, void* ws, size_t ws_bytes,
+                                   void* stream);
 
 /* ------------------------------------------------------------------------
  * Segmentation posteriors under the chain: the sum half of

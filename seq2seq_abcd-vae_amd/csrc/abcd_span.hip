@@ -127,7 +127,11 @@ __global__ __launch_bounds__(256) void span_nll(const float* __restrict__ X, lon
   const int ti = tid >> 4, tj = tid & 15;
   const int nch = (F + EM_FC - 1) / EM_FC;  // passes per step
   const int nit = nst * nch;
-  for (int p0 = 0; p0 < P; p0 += EM_TP) {
+  // gridDim.y > 1 (SPAN_TABLE without the best outputs, where nothing is folded across the prototype tiles): one
+  // workgroup per tile, so a short slice of a recording (s3.15) still fills the device; otherwise all tiles in turn
+  const int pfirst = gridDim.y > 1 ? (int)blockIdx.y * EM_TP : 0;
+  const int pend = gridDim.y > 1 ? min(P, pfirst + EM_TP) : P;
+  for (int p0 = pfirst; p0 < pend; p0 += EM_TP) {
     EmRegs g;
     auto fetch = [&](int it) {
       const int t = it / nch, c = it % nch, f = c * EM_FC + lane;
@@ -612,6 +616,137 @@ static size_t span_chain_lds(int K) {
          (K <= SC_RES_K ? (size_t)K * K * sizeof(float) : 0);
 }
 
+// The step, shared by span_chain and span_chain_win (s3.15); the whole workgroup
+// calls each function with a barrier between them.  `row` is the table's row
+// of end n: n itself for the whole table, n - row0 for a window.
+// ---- phase A: the best segment of each k that ends at n
+DEV void sc_phase_a(const double* __restrict__ T, long ldk, long row, const double* U, long n, int D, int K, int dmin,
+                    int lane, int w, int nw, double* pv, int* pa) {
+  const int dmax = (int)min((long)D, n);
+  for (int k = lane; k < K; k += 64) {
+    double best = -INFINITY;
+    int bd = INT_MAX;
+    const double* const Trow = T + (row * D - 1) * ldk + k;  // + d ldk
+    const double* const Urow = U + n * K + k;                 // - d K
+#pragma unroll 4
+    for (int d = dmin + w; d <= dmax; d += nw) {
+      const double c = Urow[-(long)d * K] + Trow[(long)d * ldk];
+      if (c > best) { best = c; bd = d; }
+    }
+    pv[w * K + k] = best;
+    pa[w * K + k] = bd;
+  }
+}
+
+// the waves' partial results of phase A in wave order, then W[n]; KEEP also stores the chosen segment's table entry
+template <bool KEEP>
+DEV void sc_combine_a(const double* __restrict__ T, long ldk, long row, long n, int D, int K, int tid, int nt, int nw,
+                      const double* pv, const int* pa, double bonus, double gv, double* Wc, int32_t* back_d,
+                      double* __restrict__ W_out, double* sel) {
+  for (int k = tid; k < K; k += nt) {
+    double best = pv[k];
+    int bd = pa[k];
+    for (int i = 1; i < nw; ++i) {
+      const double b2 = pv[i * K + k];
+      const int d2 = pa[i * K + k];
+      if (b2 > best || (b2 == best && d2 < bd)) { best = b2; bd = d2; }
+    }
+    const double seg = best + bonus, gapc = Wc[k] + gv;
+    const bool vg = gapc > -INFINITY, vs = seg > -INFINITY && bd != INT_MAX;
+    double Wn = -INFINITY;
+    int choice = 0;  // 0: the gap (or nothing); d: a segment of k of d frames ends here
+    if (vg && (!vs || gapc >= seg)) Wn = gapc;
+    else if (vs) { Wn = seg; choice = bd; }
+    Wc[k] = Wn;
+    back_d[n * K + k] = choice;
+    if (W_out) W_out[n * K + k] = Wn;
+    if (KEEP) sel[n * K + k] = choice ? T[(row * D + choice - 1) * ldk + k] : -INFINITY;
+  }
+}
+
+// ---- phase B: the best way into a segment of k that starts at n
+template <bool RES>
+DEV void sc_phase_b(const double* Wc, const float* lt, const float* __restrict__ LT, long ldt, int K, int lane, int w,
+                    int nw, double* pv, int* pa) {
+  for (int k = lane; k < K; k += 64) {
+    double best = -INFINITY;
+    int bk = INT_MAX;
+#pragma unroll 4
+    for (int kp = w; kp < K; kp += nw) {
+      const double c = Wc[kp] + (double)(RES ? lt[kp * K + k] : LT[(long)kp * ldt + k]);
+      if (c > best) { best = c; bk = kp; }
+    }
+    pv[w * K + k] = best;
+    pa[w * K + k] = bk;
+  }
+}
+
+// the waves' partial results of phase B in wave order, then U[n]
+DEV void sc_combine_b(long n, int K, int tid, int nt, int nw, const double* pv, const int* pa, double G,
+                      const double* Li, double* U, int32_t* back_k) {
+  for (int k = tid; k < K; k += nt) {
+    double best = pv[k];
+    int bk = pa[k];
+    for (int i = 1; i < nw; ++i) {
+      const double b2 = pv[i * K + k];
+      const int k2 = pa[i * K + k];
+      if (b2 > best || (b2 == best && k2 < bk)) { best = b2; bk = k2; }
+    }
+    const double init = G + Li[k];
+    const bool vi = init > -INFINITY, vp = best > -INFINITY && bk != INT_MAX;
+    double Un = -INFINITY;
+    int from = -1;  // -1: the initial term (or nothing)
+    if (vi && (!vp || init >= best)) Un = init;
+    else if (vp) { Un = best; from = bk; }
+    U[n * K + k] = Un;
+    back_k[n * K + k] = from;
+  }
+}
+
+// one thread: path_score and the walk from (N, best k) into the segment lists; seg_score from the table, KEEP: from sel
+template <bool KEEP>
+DEV void sc_backtrack(const double* __restrict__ T, long ldk, int D, const double* sel, long N, int K, double G,
+                      const double* Wc, const double* Li, const float* __restrict__ LT, long ldt,
+                      const int32_t* back_d, const int32_t* back_k, double* __restrict__ path_score,
+                      int32_t* __restrict__ n_segments, int32_t* __restrict__ seg_onset,
+                      int32_t* __restrict__ seg_length, int32_t* __restrict__ seg_cat, double* __restrict__ seg_score,
+                      double* __restrict__ seg_link) {
+  double best = G > -INFINITY ? G : -INFINITY;  // "no segment" wins a tie, then the lowest k
+  int kb = -1;
+  for (int k = 0; k < K; ++k)
+    if (Wc[k] > best) { best = Wc[k]; kb = k; }
+  *path_score = best;
+  int count = 0;
+  {
+    long n = N;
+    int k = kb;
+    while (k >= 0 && n > 0) {
+      const int d = back_d[n * K + k];
+      if (d == 0) { --n; continue; }
+      ++count;
+      n -= d;
+      k = back_k[n * K + k];
+    }
+  }
+  *n_segments = count;
+  int i = count;
+  long n = N;
+  int k = kb;
+  while (k >= 0 && n > 0) {
+    const int d = back_d[n * K + k];
+    if (d == 0) { --n; continue; }
+    --i;
+    seg_onset[i] = (int32_t)(n - d);
+    seg_length[i] = d;
+    seg_cat[i] = k;
+    seg_score[i] = KEEP ? sel[n * K + k] : T[(n * D + d - 1) * ldk + k];
+    n -= d;
+    const int from = back_k[n * K + k];
+    seg_link[i] = from < 0 ? Li[k] : (double)LT[(long)from * ldt + k];
+    k = from;
+  }
+}
+
 template <bool RES>
 __global__ __launch_bounds__(SC_THREADS) void span_chain(
     const double* __restrict__ T, long ldk, long N, int D, int K, int dmin, const float* __restrict__ gap, double bonus,
@@ -747,6 +882,84 @@ __global__ __launch_bounds__(SC_THREADS) void span_chain(
     seg_link[i] = from < 0 ? Li[k] : (double)LT[(long)from * ldt + k];
     k = from;
   }
+}
+
+// span_chain in windows of ends: steps n0 .. n1 of the same
+// recurrences with span_chain's launch widths, partition, tie rules and LDS
+// plan, the step being the sc_* functions above.  T is a window of the table:
+// its row 0 is absolute end row0, so step n reads row n - row0 (rows n0 - row0
+// .. n1 - row0 and nothing else).  What the next launch needs is carried in the
+// workspace: the lattice U (phase B runs at n1 too unless n1 = N, so U[n1] is
+// there), the two back-pointer planes, `sel` (the chosen segment's table entry
+// per (n, k): the table is gone by backtrack time) and the carry block, W[n1]
+// (K doubles), G[n1] and next_n = n1 + 1.  n0 = 1 initialises as span_chain
+// does; any other n0 must equal the carried next_n, otherwise the launch
+// writes path_score = NaN and n_segments = -1 and touches nothing else.  The
+// launch with n1 = N writes path_score and walks the back-pointers.  log_init
+// and (RES) log_trans are reloaded into LDS by every launch.
+template <bool RES>
+__global__ __launch_bounds__(SC_THREADS) void span_chain_win(
+    const double* __restrict__ T, long ldk, long row0, long n0, long n1, long N, int D, int K, int dmin,
+    const float* __restrict__ gap, double bonus, const float* __restrict__ LT, long ldt, const float* __restrict__ LI,
+    double* __restrict__ path_score, int32_t* __restrict__ n_segments, int32_t* __restrict__ seg_onset,
+    int32_t* __restrict__ seg_length, int32_t* __restrict__ seg_cat, double* __restrict__ seg_score,
+    double* __restrict__ seg_link, double* __restrict__ W_out, double* U, int32_t* back_d, int32_t* back_k,
+    double* sel, double* carry) {
+  extern __shared__ __attribute__((aligned(16))) double sc_lds[];
+  double* const Wc = sc_lds;                        // W[n][k]
+  double* const Li = Wc + K;                        // log_init, widened
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int nt = blockDim.x, nw = nt >> 6;
+  double* const pv = Li + K;                        // the waves' partial maxima, nw x K
+  int* const pa = (int*)(pv + nw * K);              // and their arguments
+  const float* const lt = (const float*)(pa + nw * K);  // RES: K x K
+  long* const next_n = (long*)(carry + K + 1);
+  const bool fresh = n0 == 1;
+  if (!fresh && *next_n != n0) {  // uniform: every thread reads the same word, nobody has written it yet
+    if (tid == 0) {
+      *path_score = __builtin_nan("");
+      *n_segments = -1;
+    }
+    return;
+  }
+  for (int k = tid; k < K; k += nt) {
+    const double li = (double)LI[k];
+    Li[k] = li;
+    if (fresh) {
+      Wc[k] = -INFINITY;
+      U[k] = li;  // G[0] = 0 and W[0] = -inf: the initial term
+      back_k[k] = -1;
+      if (W_out) W_out[k] = -INFINITY;
+    } else {
+      Wc[k] = carry[k];
+    }
+  }
+  if (RES) {
+    float* const dst = (float*)(pa + nw * K);
+    for (int i = tid; i < K * K; i += nt) dst[i] = LT[(long)(i / K) * ldt + i % K];
+  }
+  double G = fresh ? 0.0 : carry[K];
+  __syncthreads();
+  for (long n = n0; n <= n1; ++n) {
+    const double gv = gap ? (double)gap[n - 1] : -INFINITY;
+    G = G + gv;
+    sc_phase_a(T, ldk, n - row0, U, n, D, K, dmin, lane, w, nw, pv, pa);
+    __syncthreads();
+    sc_combine_a<true>(T, ldk, n - row0, n, D, K, tid, nt, nw, pv, pa, bonus, gv, Wc, back_d, W_out, sel);
+    __syncthreads();
+    if (n == N) break;
+    sc_phase_b<RES>(Wc, lt, LT, ldt, K, lane, w, nw, pv, pa);
+    __syncthreads();
+    sc_combine_b(n, K, tid, nt, nw, pv, pa, G, Li, U, back_k);
+    __syncthreads();
+  }
+  for (int k = tid; k < K; k += nt) carry[k] = Wc[k];
+  if (tid != 0) return;
+  carry[K] = G;
+  *next_n = n1 + 1;
+  if (n1 != N) return;
+  sc_backtrack<true>(nullptr, 0, D, sel, N, K, G, Wc, Li, LT, ldt, back_d, back_k, path_score, n_segments, seg_onset,
+                     seg_length, seg_cat, seg_score, seg_link);
 }
 
 // The sum form of span_chain: one workgroup, one launch, both
@@ -1095,7 +1308,9 @@ static int span_pass(const float* x, long ld_x, long N, int F, int P, int D, int
   if (N == 0) return 0;
   double* Otab = (double*)ws;
   span_prefix<<<cdiv(P, 256), 256, 0, s>>>(proto_offset_logits, P, D, Otab);
-  span_nll<MODE><<<cdiv(N, EM_TR), 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
+  // the table alone: the prototype tiles are independent and run side by side
+  const dim3 grid((unsigned)cdiv(N, EM_TR), MODE == SPAN_TABLE && !best ? (unsigned)cdiv(P, EM_TP) : 1u);
+  span_nll<MODE><<<grid, 256, 0, s>>>(x, ld_x, N, F, P, D, proto_mu, ld_mu, proto_lv, ld_lv, Otab,
                                                 log_weight, span_score, span_cat, out, ld_span, ld_k);
   ABCD_CHECK_LAUNCH();
   return 0;
@@ -1263,6 +1478,45 @@ extern "C" int abcd_span_chain_viterbi(const double* table, long ld_k, long N, i
   chain_launch(span_chain<true>, span_chain<false>, K, span_chain_lds(K), s, table, ld_k, N, D, K, d_min, gap,
                seg_bonus, log_trans, ld_trans, log_init, path_score, n_segments, seg_onset, seg_length, seg_cat,
                seg_score, seg_link, W_out, U, back_d, back_k);
+  ABCD_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" size_t abcd_span_chain_window_workspace_bytes(long N, int D, int K) {
+  if (K < 1 || K > SC_MAX_K || !span_shape_ok(N, D)) return 0;
+  // U and sel, the two back-pointer planes, then the carry block (W[n], G, next_n)
+  return ((size_t)N + 1) * (size_t)K * (2 * sizeof(double) + 2 * sizeof(int32_t)) + ((size_t)K + 2) * sizeof(double) +
+         256;
+}
+
+extern "C" int abcd_span_chain_viterbi_window(const double* table, long ld_k, long row0, long rows, long n0, long n1,
+                                              long N, int D, int K, int d_min, const float* gap, double seg_bonus,
+                                              const float* log_trans, long ld_trans, const float* log_init,
+                                              double* path_score, int32_t* n_segments, int32_t* seg_onset,
+                                              int32_t* seg_length, int32_t* seg_cat, double* seg_score,
+                                              double* seg_link, double* W_out, void* ws, size_t ws_bytes,
+                                              void* stream) {
+  ABCD_REQUIRE(K >= 1 && K <= SC_MAX_K && span_shape_ok(N, D) && d_min >= 1 && d_min <= D);
+  ABCD_REQUIRE(1 <= n0 && n0 <= n1 && n1 <= N);
+  ABCD_REQUIRE(row0 >= 0 && row0 <= std::max(0L, n0 - D) && rows >= 1 && n1 - row0 < rows);
+  ABCD_REQUIRE(ld_k >= K && ld_k < (1L << 31) && ld_trans >= K);
+  ABCD_REQUIRE(rows < (1L << 31) && rows * (long)D < (1L << 31) && rows * (long)D * ld_k < (1L << 31));
+  ABCD_REQUIRE(table && log_trans && log_init && path_score && n_segments && seg_onset && seg_length && seg_cat &&
+               seg_score && seg_link);
+  const size_t need = abcd_span_chain_window_workspace_bytes(N, D, K);
+  ABCD_REQUIRE(need && ws && ws_bytes >= need);
+  hipStream_t s = (hipStream_t)stream;
+  ABCD_TRY(raise_lds<span_chain_win<true>>(span_chain_lds(SC_RES_K)));
+  ABCD_TRY(raise_lds<span_chain_win<false>>(std::max(span_chain_lds(SC_WIDE_K), span_chain_lds(SC_MAX_K))));
+  const long cells = (N + 1) * K;
+  double* U = (double*)ws;
+  double* sel = U + cells;
+  int32_t* back_d = (int32_t*)(sel + cells);
+  int32_t* back_k = back_d + cells;
+  double* carry = (double*)(back_k + cells);  // 16 cells bytes in: 8-byte aligned
+  chain_launch(span_chain_win<true>, span_chain_win<false>, K, span_chain_lds(K), s, table, ld_k, row0, n0, n1, N, D, K,
+               d_min, gap, seg_bonus, log_trans, ld_trans, log_init, path_score, n_segments, seg_onset, seg_length,
+               seg_cat, seg_score, seg_link, W_out, U, back_d, back_k, sel, carry);
   ABCD_CHECK_LAUNCH();
   return 0;
 }

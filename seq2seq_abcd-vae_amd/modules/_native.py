@@ -182,6 +182,11 @@ _SIGS = {
     "abcd_span_chain_viterbi": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_double, c_void_p,
                                         c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "abcd_span_chain_window_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "abcd_span_chain_viterbi_window": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_long, c_long, c_int, c_int,
+                                               c_int, c_void_p, c_double, c_void_p, c_long, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                               c_void_p, c_size_t, c_void_p]),
     "abcd_span_chain_posterior_plan": (c_int, [c_int, c_int, _P(c_int), _P(c_int), _P(c_size_t)]),
     "abcd_span_chain_posterior_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
     "abcd_span_chain_posterior": (c_int, [c_void_p, c_long, c_long, c_int, c_int, c_int, c_void_p, c_double, c_double,

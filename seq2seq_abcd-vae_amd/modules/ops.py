@@ -36,10 +36,15 @@ operator                   replaces (reference)                            C ent
 ``abcd::span_table``       (none: span scores of every category)           ``abcd_span_table``
 ``abcd::span_chain_viterbi`` (none: the best cover under a category chain) ``abcd_span_chain_viterbi``
 ``abcd::span_chain_posterior`` (none: posteriors and counts under the chain) ``abcd_span_chain_posterior``
+``abcd::span_chain_viterbi_window`` (none: that cover, the table in windows) ``abcd_span_chain_viterbi_window``
 =========================  ==============================================  =========================================
 
-The last fifteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
+The last sixteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
+
+``span_chain_viterbi_window`` is the one operator that is NOT functional: it
+carries a recording's programme from call to call in a state tensor it mutates
+(``STATEFUL_OPS``; ``OPS`` lists the functional ones).
 
 Operators take tensors, ints and floats only (no module objects): the
 configuration travels as an ``int[]`` in the C struct's field order, the
@@ -1160,6 +1165,78 @@ def _(table, d_min, gap, seg_bonus, log_trans, log_init, want_w):
 _forward_only(span_chain_viterbi, "span_chain_viterbi")
 
 
+def span_chain_window_state(n, D, K, device):
+    """The state tensor ``span_chain_viterbi_window`` carries a recording of
+    ``n`` frames in (uint8; abcd_span_chain_window_workspace_bytes: the lattice,
+    the back-pointers, the chosen entries and the carry block, 24 (n + 1) K
+    bytes and a little).  Its contents mean nothing outside the operator."""
+    nbytes = N.lib().abcd_span_chain_window_workspace_bytes(int(n), int(D), int(K))
+    if nbytes == 0:
+        raise N.HipError(f"span_chain_viterbi_window: unsupported shape (D > 16383, (N + 1) * D >= 2^31 or K > 1024); "
+                         f"N = {n}, D = {D}, K = {K}")
+    return N.workspace(nbytes, device)
+
+
+@torch.library.custom_op("abcd::span_chain_viterbi_window", mutates_args=("state", "W"))
+def span_chain_viterbi_window(table: Tensor, row0: int, n0: int, n1: int, n: int, d_min: int, gap: Optional[Tensor],
+                              seg_bonus: float, log_trans: Tensor, log_init: Tensor, state: Tensor,
+                              W: Optional[Tensor]) -> List[Tensor]:
+    """Steps n0 .. n1 of span_chain_viterbi's programme over a recording of n
+    frames on a WINDOW of the table (rows x D x K, its row 0 the absolute end
+    row0 <= max(0, n0 - D), rows > n1 - row0), the programme being carried from
+    call to call in ``state`` (span_chain_window_state; mutated) and, when
+    given, rows n0 .. n1 of W ((n + 1) x K fp64; mutated) being written
+    (abcd_span_chain_viterbi_window).  The calls of a recording run in order on
+    one stream: n0 = 1 first, then every n0 the previous n1 + 1.  -> span_chain_
+    viterbi's [path_score, n_segments, onset, length, category, score, link],
+    written by the call with n1 = n; before that, and after a call out of
+    order, path_score is NaN and n_segments -1.  gap holds the n scores of the
+    whole recording."""
+    rows, D, K, d_min, lt, ldt, li = _chain_args("span_chain_viterbi_window", table, d_min, log_trans, log_init)
+    rows += 1
+    row0, n0, n1, n = int(row0), int(n0), int(n1), int(n)
+    if not 1 <= n0 <= n1 <= n:
+        raise ValueError(f"span_chain_viterbi_window: 1 <= n0 <= n1 <= N, got {n0}, {n1} and N = {n}")
+    if not (0 <= row0 <= max(0, n0 - D) and n1 - row0 < rows):
+        raise ValueError(f"span_chain_viterbi_window: the window must start at 0 <= row0 <= max(0, n0 - D) and hold "
+                         f"end n1; got row0 = {row0}, {rows} rows, n0 = {n0}, n1 = {n1}, D = {D}")
+    dev = table.device
+    tb = table.double().contiguous()
+    g = _gap_arg("span_chain_viterbi_window", gap, n)
+    L_ = N.lib()
+    nbytes = L_.abcd_span_chain_window_workspace_bytes(n, D, K)
+    N.require_gpu(state)
+    if nbytes == 0 or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
+        raise ValueError(f"span_chain_viterbi_window: state must be span_chain_window_state({n}, {D}, {K})")
+    if W is not None:
+        N.require_gpu(W)
+        if tuple(W.shape) != (n + 1, K) or W.dtype != torch.float64 or not W.is_contiguous():
+            raise ValueError(f"span_chain_viterbi_window: W must be {(n + 1, K)} contiguous float64")
+    cap = n // d_min
+    outs = _segment_lists(cap, dev, True)
+    outs[0].fill_(float("nan"))
+    outs[1].fill_(-1)
+    N.check(L_.abcd_span_chain_viterbi_window(N.ptr(tb), K, row0, rows, n0, n1, n, D, K, d_min, N.ptr(g),
+                                              float(seg_bonus), N.ptr(lt), ldt, N.ptr(li), *(N.ptr(t) for t in outs),
+                                              N.ptr(W), N.ptr(state), state.numel(), N.stream()),
+            "span chain viterbi window")
+    return outs[:2] + [t[:cap] for t in outs[2:]]
+
+
+@span_chain_viterbi_window.register_fake
+def _(table, row0, n0, n1, n, d_min, gap, seg_bonus, log_trans, log_init, state, W):
+    cap = int(n) // int(d_min)
+    e = table.new_empty
+    return [e((), dtype=torch.float64), e((), dtype=torch.int32), e(cap, dtype=torch.int32),
+            e(cap, dtype=torch.int32), e(cap, dtype=torch.int32), e(cap, dtype=torch.float64),
+            e(cap, dtype=torch.float64)]
+
+
+# torch.library takes no autograd formula for an operator that mutates an argument, so _forward_only does not apply:
+# torch's own fallback makes backward through the outputs raise ("not implemented"), and every caller runs under
+# torch.no_grad().
+
+
 @torch.library.custom_op("abcd::span_chain_posterior", mutates_args=())
 def span_chain_posterior(table: Tensor, d_min: int, gap: Optional[Tensor], seg_bonus: float, scale: float,
                          log_trans: Tensor, log_init: Tensor, want_counts: bool, want_table: bool) -> List[Tensor]:
@@ -1378,6 +1455,7 @@ OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sa
        "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
        "warp_nll", "warp_path", "span_evidence", "span_posterior", "span_table", "span_chain_viterbi",
        "span_chain_posterior")
+STATEFUL_OPS = ("span_chain_viterbi_window",)  # mutate a state argument: kept apart from the functional OPS
 
 
 def registered() -> Sequence[str]:

@@ -16,10 +16,15 @@ gap and span posteriors over every cover and the recording's log evidence
 categories of consecutive segments inside the programme
 (``ops.span_table`` / ``ops.span_chain_viterbi``); ``count_transitions`` and
 ``refit_transitions`` fit that chain on uncut recordings by Viterbi training.
+``segment_frames(..., window_frames=W)`` runs the same programme on recordings
+whose whole table does not fit: ``plan_windows`` cuts the ends into windows,
+each window's table is built from a slice of the frames and
+``ops.span_chain_viterbi_window`` carries the programme across them.
 ``segment_chain_posteriors`` is the sum half of that programme (onset, end,
 gap, span and label posteriors, the evidence and the expected bigram counts
 under the chain, ``ops.span_chain_posterior``) and ``refit_transitions_em``
 fits the chain by EM on those counts."""
+import bisect
 import math
 
 import torch
@@ -29,7 +34,7 @@ from . import ops
 
 
 def segment_frames(decoder, prototypes, frames, max_length, min_length=1, log_weight=None, gap=None, seg_bonus=0.0,
-                   posteriors=False, temperature=1.0, transitions=None, include_weight=False):
+                   posteriors=False, temperature=1.0, transitions=None, include_weight=False, window_frames=None):
     """The best segmentation of ``frames`` (N x F on the GPU): a dict of
     ``onset``, ``length``, ``category`` (int64, one entry per segment in time
     order, frames), ``score`` (float64: each segment's ``log_weight[cat] - em -
@@ -65,11 +70,36 @@ def segment_frames(decoder, prototypes, frames, max_length, min_length=1, log_we
     (int64: the lowest argmax over k of ``table[e, d, :] + log_weight`` at the
     chosen span, what the span alone would have been labelled).
     ``path_score`` sums scores, links, bonuses and gaps.  Together with
-    ``posteriors=True`` this raises ValueError."""
+    ``posteriors=True`` this raises ValueError.
+
+    ``window_frames`` (with ``transitions`` only; None: the whole table at
+    once, which stops at ``(N + 1) max_length K < 2^31``) cuts a long recording
+    into windows of that many ends (``plan_windows``): each window's table is
+    built from a slice of the frames, ``ops.span_chain_viterbi_window`` runs
+    the window's steps and carries the programme to the next, and the table is
+    freed.  The dict is the one-shot dict, bit for bit, for every
+    ``window_frames >= 1``.  Peak table memory is ``8 (n1 - row0 + 1)
+    max_length K`` bytes, at most ``8 (window_frames + max_length + 32)
+    max_length K``, whatever N; the carried state takes ``24 (N + 1) K``.
+    ``context_free_category`` needs the chosen spans under every category: a
+    second sweep rebuilds the tables of the windows that hold the end of a
+    chosen segment.  Together with ``posteriors=True`` this raises
+    ValueError."""
     N.require_gpu(frames)
     n, D, d_min = int(frames.shape[0]), int(max_length), int(min_length)
     if not 1 <= d_min <= D:
         raise ValueError(f"segment_frames: 1 <= min_length <= max_length, got {d_min} and {D}")
+    if window_frames is not None:
+        if posteriors:
+            raise ValueError("segment_frames: posteriors are not available in windows; give window_frames or "
+                             "posteriors=True, not both")
+        if transitions is None:
+            raise ValueError("segment_frames: window_frames cuts the table of the programme under a transition "
+                             "model; give transitions too")
+        if int(window_frames) < 1:
+            raise ValueError(f"segment_frames: window_frames must be at least 1, got {window_frames}")
+        return _segment_chain_windows(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions,
+                                      include_weight, int(window_frames))
     if transitions is not None:
         if posteriors:
             raise ValueError("segment_frames: posteriors under a transition model are not available; give "
@@ -113,10 +143,83 @@ def _chain_setup(name, transitions, prototypes, device):
     return lt, li, K
 
 
+TABLE_ALIGN = 32  # the table pass's start tile (EM_TR of csrc/abcd_emtile.h)
+
+
+def plan_windows(N, D, window_frames, align=TABLE_ALIGN):
+    """The windows ``segment_frames(window_frames=...)`` cuts a recording of N
+    frames into: a list of ``(row0, n0, n1)``, the ends ``1 .. N`` exactly once
+    and in order, ``n1 - n0 + 1 <= window_frames``, and ``row0 = align *
+    floor(max(0, n0 - D) / align)`` the frame the window's table starts at: a
+    segment of up to D frames that ends at n0 starts no earlier, and a start
+    that is a multiple of the table pass's tile puts every span at the place
+    of its tile, on the thread, it has in the pass over the whole recording, so
+    the window's entries have the whole table's bits.  The window's table is
+    ``span_table(frames[row0:n1])``, ``8 (n1 - row0 + 1) D K`` bytes
+    (``window_table_bytes``), at most ``8 (window_frames + D + align) D K``.
+    A pure function."""
+    N, D, W, align = int(N), int(D), int(window_frames), int(align)
+    if N < 0 or D < 1 or W < 1 or align < 1:
+        raise ValueError(f"plan_windows: N >= 0 and D, window_frames, align >= 1, got {N}, {D}, {W}, {align}")
+    plan, n0 = [], 1
+    while n0 <= N:
+        n1 = min(N, n0 + W - 1)
+        plan.append((align * (max(0, n0 - D) // align), n0, n1))
+        n0 = n1 + 1
+    return plan
+
+
+def window_table_bytes(window, D, K):
+    """The bytes of one ``plan_windows`` window's table over K categories."""
+    row0, _, n1 = window
+    return 8 * (int(n1) - int(row0) + 1) * int(D) * int(K)
+
+
+def _segment_chain_windows(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions,
+                           include_weight, window_frames):
+    """segment_frames under a transition model with the table in windows (see there)."""
+    if int(frames.shape[0]) == 0:   # nothing to carry: the one-shot entry point's empty path
+        return _segment_chain(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions,
+                              include_weight)
+    lt, li, K = _chain_setup("segment_frames", transitions, prototypes, frames.device)
+    lw = None if log_weight is None else torch.as_tensor(log_weight, device=frames.device).float().reshape(-1)
+    tlw = lw if include_weight else None
+    n = int(frames.shape[0])
+    plan = plan_windows(n, D, window_frames)
+    with torch.no_grad():
+        g = None if gap is None else torch.as_tensor(gap, device=frames.device).float()
+        state = ops.span_chain_window_state(n, D, K, frames.device)
+        for row0, n0, n1 in plan:
+            table, _, _ = decoder.span_table(prototypes, frames[row0:n1], D, log_weight=tlw)
+            ps, ns, onset, length, category, seg, link = ops.span_chain_viterbi_window(
+                table, row0, n0, n1, n, d_min, g, float(seg_bonus), lt, li, state, None)
+            del table
+        k = int(ns)
+        if k < 0:
+            raise RuntimeError("segment_frames: the windows of the programme ran out of order")
+        onset, length = onset[:k].to(torch.int64), length[:k].to(torch.int64)
+        # the second sweep: the chosen spans under every category, from the windows that hold a chosen end
+        ends = (onset + length).tolist()                        # ascending
+        v = torch.empty(k, K, dtype=torch.float64, device=frames.device)
+        for row0, n0, n1 in plan:
+            a, b = bisect.bisect_left(ends, n0), bisect.bisect_right(ends, n1)
+            if a == b:
+                continue
+            table, _, _ = decoder.span_table(prototypes, frames[row0:n1], D, log_weight=tlw)
+            v[a:b] = table[onset[a:b] + length[a:b] - row0, length[a:b] - 1]
+            del table
+        return _chain_dict(ps, k, onset, length, category, seg, link, v, lw, include_weight, K)
+
+
 def _segment_chain(decoder, prototypes, frames, D, d_min, log_weight, gap, seg_bonus, transitions, include_weight):
     """segment_frames under a transition model (see there)."""
     lt, li, K = _chain_setup("segment_frames", transitions, prototypes, frames.device)
     lw = None if log_weight is None else torch.as_tensor(log_weight, device=frames.device).float().reshape(-1)
+    n = int(frames.shape[0])
+    if (N.lib().abcd_span_table_workspace_bytes(n, D, K, K) == 0
+            and N.lib().abcd_span_chain_window_workspace_bytes(n, D, K) != 0):
+        raise N.HipError(f"segment_frames: the whole table is beyond its index limit (N + 1) * D * K < 2^31 (N = {n}, "
+                         f"D = {D}, K = {K}); give window_frames (1024, say) to build it in windows")
     with torch.no_grad():
         table, _, _ = decoder.span_table(prototypes, frames, D, log_weight=lw if include_weight else None)
         g = None if gap is None else torch.as_tensor(gap, device=frames.device).float()
@@ -131,6 +234,12 @@ def _chain_cut(table, d_min, g, seg_bonus, lt, li, lw, include_weight, K):
     k = int(ns)
     onset, length = onset[:k].to(torch.int64), length[:k].to(torch.int64)
     v = table[onset + length, length - 1]                   # k x K: the chosen spans under every category
+    return _chain_dict(ps, k, onset, length, category, seg, link, v, lw, include_weight, K)
+
+
+def _chain_dict(ps, k, onset, length, category, seg, link, v, lw, include_weight, K):
+    """``segment_frames(transitions=...)``'s dict from the programme's outputs and ``v`` (k x K: the table's rows at
+    the chosen spans)."""
     if lw is not None and not include_weight:
         v = v + lw.double()[None, :]
     v = torch.nan_to_num(v, nan=-math.inf, posinf=math.inf, neginf=-math.inf)

@@ -43,7 +43,10 @@ Viterbi training of the matrix on the recordings first and writes it to
 bigram counts over every labelled cover instead.  ``--chain_posteriors`` sums
 over every labelled cover under the chain (``segmentation.segment_chain_posteriors``)
 and appends ``onset_posterior``, ``offset_posterior``, ``span_posterior`` and
-``label_posterior``: how far to trust each cut and each label."""
+``label_posterior``: how far to trust each cut and each label.
+``--window_frames W`` (with ``--transitions``) cuts long recordings' tables into
+windows of W ends: the same segments, bit for bit, at a table memory that does
+not grow with the recording."""
 import os
 import sys
 
@@ -171,17 +174,20 @@ class Segmenter(classify.Classifier):
     """A trained ABCD checkpoint opened for segmentation."""
 
     def segment_recording(self, frames, max_length, min_length=1, log_weight=None, gap=None, seg_bonus=0.0,
-                          speaker=None, posteriors=False, temperature=1.0, transitions=None):
+                          speaker=None, posteriors=False, temperature=1.0, transitions=None, window_frames=None):
         """``segmentation.segment_frames`` of one recording's frames under the
         categories' prototypes (of ``speaker`` when the decoder embeds speakers);
         ``transitions``: a TransitionModel for the programme with category
-        transitions."""
+        transitions; ``window_frames``: that programme with the table in
+        windows of so many ends."""
         if self.decoder.embed_speaker is not None and speaker is None:
             raise ValueError("this decoder embeds speakers: a speaker index is required")
         protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(max_length))
         extra = dict(posteriors=True, temperature=temperature) if posteriors else {}
         if transitions is not None:
             extra["transitions"] = transitions
+        if window_frames is not None:
+            extra["window_frames"] = window_frames
         return segmentation.segment_frames(self.decoder, protos, frames.to(self.device), max_length,
                                            min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus,
                                            **extra)
@@ -257,7 +263,24 @@ def get_parameters(argv=None):
                         "the chain and append onset_posterior, offset_posterior, span_posterior and label_posterior; "
                         "--posterior_temperature, --curves_dir (which also holds each frame's most probable category "
                         "and its probability) and --recordings_out apply")
+    p.add_argument("--window_frames", type=int, default=None,
+                   help="with --transitions: build the per-category table in windows of this many end frames "
+                        "instead of at once, for recordings whose whole table (8 (N + 1) max_length K bytes, (N + 1) "
+                        "max_length K < 2^31) does not fit; the same segments bit for bit at a peak table memory of at "
+                        "most 8 (W + max_length + 32) max_length K bytes whatever the recording's length; 1024 is a "
+                        "good value")
     a = p.parse_args(argv)
+    if a.window_frames is not None:
+        if a.window_frames < 1:
+            p.error("--window_frames must be at least 1")
+        if a.transitions is None:
+            p.error("--window_frames needs --transitions: it cuts the table of the programme under a transition model")
+        if a.chain_posteriors:
+            p.error("--window_frames cannot be combined with --chain_posteriors: the sum over every labelled cover "
+                    "sweeps the whole table backwards and is not available in windows")
+        if a.refit_transitions > 0 and a.refit_method == "em":
+            p.error("--window_frames cannot be combined with --refit_method em: its expected counts come from the sum "
+                    "over every labelled cover, which is not available in windows; use --refit_method viterbi")
     if a.chain_posteriors and a.transitions is None and a.refit_transitions <= 0:
         p.error("--chain_posteriors needs --transitions or --refit_transitions")
     if a.refit_method != "viterbi" and a.refit_transitions <= 0:
@@ -355,7 +378,8 @@ def main(argv=None):
         _, _, _, _, frames, d_min, gap = got or prepare(path)
         return seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
                                      seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
-                                     temperature=a.posterior_temperature, transitions=transitions)
+                                     temperature=a.posterior_temperature, transitions=transitions,
+                                     window_frames=a.window_frames if transitions is not None else None)
 
     def posterior(path, transitions, got=None, **kw):
         _, _, _, _, frames, d_min, gap = got or prepare(path)
