@@ -114,7 +114,8 @@ int abcd_encoder_backward_dropout(const abcd_encoder_cfg* cfg, const abcd_encode
  * stride ldx), Hprev[d]: K x H (stride H; the hidden state each frame's step
  * consumed, zero where it had no predecessor).  b_hh[d] may be NULL.  The
  * encoder backward runs this after its BPTT (layer 0); at F <= 143 with
- * roundup16(F) = 144 and H = 256 it is one gemm_wg3b launch + one slab reduction. */
+ * roundup16(F) = 144 and H = 256 it is one gemm_wg3b launch + one slab reduction.
+ * K = 0 returns 0 and writes nothing (the gradients are not zeroed). */
 size_t abcd_lstm_wgrad_workspace_bytes(int nd, int F, int H, int K);
 int abcd_lstm_wgrad(int nd, int F, int H, int K, const float* const* dG, const float* X, long ldx,
                     const float* const* Hprev, float* const* w_ih, float* const* b_ih, float* const* b_hh,
@@ -1122,10 +1123,52 @@ void abcd_dispatch_reset(void);
  * side-stream GEMM mode, the one the training step enters beside a
  * persistent recurrent kernel: abcd_gemm_nt / abcd_gemm_tn then take the
  * small-footprint routes.  For tests; nothing in the training path calls
- * either. */
+ * either;
+ * abcd_debug_offset_head_fwd -- the decoder's fused offset head forward on
+ * the caller's buffers, as the decoder forward runs it: Zo = tanh(Hs W1o^T +
+ * b1o) (M x N at stride N; Hs M x K at stride ldh, W1o N x K) with part[m *
+ * nsl + slice] = the 64-column slice's share of Zo . w2 (nsl = ceil(N / 64)),
+ * then logit = sum of the partials in slice order + b2[0] and, with tgt,
+ * bce / dlog_raw (tgt NULL: neither is touched).  *fused_out = 1 when the
+ * fused form ran ("x6r8<8,64,offset_fwd>"); 0 when it declines (K > 256, K % 8,
+ * N % 4, ldh % 4, Hs / W1o / Zo not 16-B aligned, Hs or W1o of 2 GiB or
+ * more): nothing is launched;
+ * abcd_debug_offset_head_bwd -- its backward: dlog_s = s_off[0] dlog_raw,
+ * dZo = dlog_s w2 (1 - Zo^2) (M x K at stride K) and DHO = dZo W1oT^T (M x N
+ * at stride N; W1oT N x K), "x6r8<8,64,offset_bwd>"; *fused_out as above
+ * (it declines on the same conditions, DHO and dZo for Zo, and also where a
+ * workgroup's row range is so long that its LDS request passes 160 KiB:
+ * more than 7424 rows per range, M above about 118000 at 16 slices);
+ * abcd_debug_gemm_tn_batch -- up to 8 jobs C_j = alpha_j A_j^T B_j + beta_j
+ * C_j (A_j K x M at stride lda, B_j K x N at stride ldb) in the one launch
+ * the sampler backward uses (abcd_debug_gemm_route then reads
+ * "tn_batch<1,1,64>", or "tn_batch<2,2,16>" in side mode: the instance the
+ * launcher started); the job fields as arrays of n.  A job with M or
+ * N = 0 is skipped; n > 8, M % 4, N % 4, lda % 4, ldb % 4 or an A / B not
+ * 16-B aligned return an error before any launch;
+ * abcd_debug_colsum_batch -- up to 8 jobs out_j[c] = beta_j out_j[c] + sum_r
+ * w_j[r] Z_j[r * ldz + c] (w_j NULL: 1; out2_j, optional, receives the same)
+ * in the decoder backward's two launches; scratch holds every job's partial
+ * sums and clamps their slice counts; too little of it for a job's one slice
+ * returns an error before any launch.
+ * All four are host-only wrappers that launch existing kernels under the
+ * launchers' own preconditions and return ABCD_EINVAL on null or negative
+ * arguments.  For tests; nothing in the training path calls them. */
 void abcd_debug_persist_prof(unsigned long long* dev_buf, int mask);
 const char* abcd_debug_gemm_route(void);
 void abcd_debug_gemm_side(int on);
+int abcd_debug_offset_head_fwd(int M, int N, int K, const float* Hs, long ldh, const float* W1o, const float* b1o,
+                               const float* w2, const float* b2, const float* tgt, float* Zo, float* part,
+                               float* logit, float* dlog_raw, float* bce, int* fused_out, void* stream);
+int abcd_debug_offset_head_bwd(int M, int N, int K, const float* Zo, const float* W1oT, const float* w2,
+                               const float* dlog_raw, const float* s_off, float* DHO, float* dZo, float* dlog_s,
+                               int* fused_out, void* stream);
+int abcd_debug_gemm_tn_batch(int n, const float* const* A, const long* lda, const float* const* B, const long* ldb,
+                             float* const* C, const long* ldc, const int* M, const int* N, const int* K,
+                             const float* alpha, const float* beta, void* stream);
+int abcd_debug_colsum_batch(int n, const float* const* Z, const long* ldz, const int* nrows, const int* ncols,
+                            const float* const* w, float* const* out, const float* beta, float* const* out2,
+                            float* scratch, size_t scratch_floats, void* stream);
 /* Side-stream gate (per calling host thread, default off): read by a deferred
  * abcd_decoder_backward_dropout(..., ABCD_DEFER_PARAMS).  The first encoder
  * BPTT this thread launches persistently after it becomes the gate's target,

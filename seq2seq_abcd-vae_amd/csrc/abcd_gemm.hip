@@ -482,8 +482,13 @@ int gemm_tn_batch(hipStream_t s, const GemmJob* jobs, int n) {
   if (!tiles) return 0;
   // 64-deep LDS slabs (70 KB) on a quiet chip; 16-deep ones (17 KB) beside a
   // persistent kernel (side mode), whose LDS image leaves ~40 KB per CU
-  if (tl_side) gemm_tn_batch_kernel<2, 2, 16><<<tiles, 256, 0, s>>>(b);
-  else gemm_tn_batch_kernel<1, 1, 64><<<tiles, 256, 0, s>>>(b);
+  if (tl_side) {
+    route_set("tn_batch<2,2,16>");
+    gemm_tn_batch_kernel<2, 2, 16><<<tiles, 256, 0, s>>>(b);
+  } else {
+    route_set("tn_batch<1,1,64>");
+    gemm_tn_batch_kernel<1, 1, 64><<<tiles, 256, 0, s>>>(b);
+  }
   ABCD_CHECK_LAUNCH();
   return 0;
 }

@@ -1128,7 +1128,11 @@ extern "C" size_t abcd_lstm_wgrad_workspace_bytes(int nd, int F, int H, int K) {
 }
 
 // C ABI: the LSTM layer's weight gradients (gemm_wg2 when the shape has an
-// instance, else the split GEMM route the encoder backward falls back to)
+// instance, else the split GEMM route the encoder backward falls back to).
+// K = 0 (no frames): returns 0 after the argument checks and writes nothing
+// -- the gradients keep what they held, they are not zeroed.  The wg forms'
+// 32-bit-offset guard (K * 4H * 4 >= 2 GiB falls back to the split GEMMs)
+// needs 2 GiB operands and is not reached by any test.
 extern "C" int abcd_lstm_wgrad(int nd, int F, int H, int K, const float* const* dG, const float* X, long ldx,
                                const float* const* Hprev, float* const* w_ih, float* const* b_ih,
                                float* const* b_hh, float* const* w_hh, void* ws, size_t ws_bytes, void* stream) {
@@ -1165,6 +1169,66 @@ extern "C" int abcd_lstm_wgrad(int nd, int F, int H, int K, const float* const* 
     ABCD_TRY((hipError_t)colsum(s, dG[d], M, K, M, nullptr, b_ih[d], 0.f, scratch, scf, b_hh ? b_hh[d] : nullptr));
   }
   return 0;
+}
+
+// diagnostics (abcd_hip.h): the fused offset head and the two batched
+// launchers on caller-owned buffers, exactly as dec_forward_impl /
+// dec_backward_impl / the sampler backward call them
+extern "C" int abcd_debug_offset_head_fwd(int M, int N, int K, const float* Hs, long ldh, const float* W1o,
+                                          const float* b1o, const float* w2, const float* b2, const float* tgt,
+                                          float* Zo, float* part, float* logit, float* dlog_raw, float* bce,
+                                          int* fused_out, void* stream) {
+  ABCD_REQUIRE(M > 0 && N > 0 && K > 0 && ldh >= K && Hs && W1o && b1o && w2 && b2 && Zo && part && logit && fused_out);
+  ABCD_REQUIRE(!tgt || (dlog_raw && bce));
+  hipStream_t s = (hipStream_t)stream;
+  bool fused = false;
+  *fused_out = 0;
+  ABCD_TRY((hipError_t)gemm_offset_fwd(s, M, N, K, Hs, ldh, W1o, b1o, Zo, w2, part, &fused));
+  if (!fused) return 0;
+  dec_offset_logit<<<cdiv(M, 256), 256, 0, s>>>(part, offset_head_slices(N), M, b2, tgt, logit, dlog_raw, bce);
+  ABCD_CHECK_LAUNCH();
+  *fused_out = 1;
+  return 0;
+}
+
+extern "C" int abcd_debug_offset_head_bwd(int M, int N, int K, const float* Zo, const float* W1oT, const float* w2,
+                                          const float* dlog_raw, const float* s_off, float* DHO, float* dZo,
+                                          float* dlog_s, int* fused_out, void* stream) {
+  ABCD_REQUIRE(M > 0 && N > 0 && K > 0 && Zo && W1oT && w2 && dlog_raw && s_off && DHO && dZo && dlog_s && fused_out);
+  bool fused = false;
+  *fused_out = 0;
+  ABCD_TRY((hipError_t)gemm_offset_bwd((hipStream_t)stream, M, N, K, Zo, W1oT, DHO, w2, dlog_raw, s_off, dZo, dlog_s,
+                                       &fused));
+  *fused_out = fused ? 1 : 0;
+  return 0;
+}
+
+extern "C" int abcd_debug_gemm_tn_batch(int n, const float* const* A, const long* lda, const float* const* B,
+                                        const long* ldb, float* const* C, const long* ldc, const int* M, const int* N,
+                                        const int* K, const float* alpha, const float* beta, void* stream) {
+  ABCD_REQUIRE(n >= 0 && (n == 0 || (A && lda && B && ldb && C && ldc && M && N && K && alpha && beta)));
+  if (n > GEMM_BATCH_MAX) return ABCD_EINVAL;
+  GemmJob jobs[GEMM_BATCH_MAX];
+  for (int i = 0; i < n; ++i) {
+    ABCD_REQUIRE(M[i] >= 0 && N[i] >= 0 && K[i] >= 0);
+    ABCD_REQUIRE(M[i] == 0 || N[i] == 0 || (A[i] && B[i] && C[i] && lda[i] >= M[i] && ldb[i] >= N[i] && ldc[i] >= N[i]));
+    jobs[i] = GemmJob{A[i], lda[i], B[i], ldb[i], C[i], ldc[i], M[i], N[i], K[i], alpha[i], beta[i]};
+  }
+  return gemm_tn_batch((hipStream_t)stream, jobs, n);
+}
+
+extern "C" int abcd_debug_colsum_batch(int n, const float* const* Z, const long* ldz, const int* nrows,
+                                       const int* ncols, const float* const* w, float* const* out, const float* beta,
+                                       float* const* out2, float* scratch, size_t scratch_floats, void* stream) {
+  ABCD_REQUIRE(n >= 0 && (n == 0 || (Z && ldz && nrows && ncols && w && out && beta && out2 && scratch)));
+  if (n > COLSUM_BATCH_MAX) return ABCD_EINVAL;
+  ColsumJob jobs[COLSUM_BATCH_MAX];
+  for (int i = 0; i < n; ++i) {
+    ABCD_REQUIRE(nrows[i] >= 0 && ncols[i] >= 0);
+    ABCD_REQUIRE(ncols[i] == 0 || (Z[i] && out[i] && ldz[i] >= ncols[i]));
+    jobs[i] = ColsumJob{Z[i], ldz[i], nrows[i], ncols[i], w[i], out[i], beta[i], out2[i]};
+  }
+  return colsum_batch((hipStream_t)stream, jobs, n, scratch, scratch_floats);
 }
 
 extern "C" size_t abcd_decoder_workspace_bytes(const abcd_decoder_cfg* c, int T, int L, int B) {

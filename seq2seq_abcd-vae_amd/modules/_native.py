@@ -238,6 +238,15 @@ _SIGS = {
     "abcd_debug_persist_prof": (None, [c_void_p, c_int]),
     "abcd_debug_gemm_route": (ctypes.c_char_p, []),
     "abcd_debug_gemm_side": (None, [c_int]),
+    "abcd_debug_offset_head_fwd": (c_int, [c_int, c_int, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           ctypes.POINTER(c_int), c_void_p]),
+    "abcd_debug_offset_head_bwd": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int), c_void_p]),
+    "abcd_debug_gemm_tn_batch": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "abcd_debug_colsum_batch": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_size_t, c_void_p]),
     "abcd_side_gate_enable": (None, [c_int]),
     "abcd_debug_xcc_map": (c_int, [c_void_p, c_int, c_void_p]),
     "abcd_fill_normal": (c_int, [c_void_p, c_long, c_uint64, c_uint64, c_void_p]),

@@ -426,13 +426,57 @@ def dump(name, rows):
     E.dump_observed("gemm_" + name, rows)
 
 
+SECTIONS = OrderedDict([("lstm_wgrad", ("lstm_wgrad",)), ("offset_head", ("offset_head_fwd", "offset_head_bwd")),
+                        ("tn_batch", ("tn_batch",)), ("colsum_batch", ("colsum_batch",))])
+
+
+def _walk(x, key=""):
+    """Every (key, value) leaf of the nested figures of one dumped row."""
+    if isinstance(x, dict):
+        for k, v in x.items():
+            yield from _walk(v, k)
+    elif isinstance(x, (int, float)) and not isinstance(x, bool):
+        yield key, x
+
+
+def section_worst(rows):
+    """The worst figures of the rows tests/test_gpu_wgrad_offset.py dumped for one group."""
+    out = dict(worst_of_bar=None, worst_u=None, maxnorm_worst_of_e32=None, mismatches=0, bce_dlog_worst_abs=None,
+               failed_checks=sum(len(k.get("fails", [])) for r in rows for k in r.get("kinds", {}).values())
+               + sum(len(r.get("fails", [])) for r in rows))
+    up = lambda k, v: out.__setitem__(k, v if out[k] is None else max(out[k], v))
+
+    def visit(d):
+        if isinstance(d, dict):
+            if d.get("e32") and d.get("e_maxnorm") is not None:
+                up("maxnorm_worst_of_e32", d["e_maxnorm"] / d["e32"])
+            for v in d.values():
+                visit(v)
+    for r in rows:
+        fig = r.get("kinds", r.get("figures", {}))
+        visit(fig)
+        for k, v in _walk(fig):
+            if k.endswith("worst_of_bar"):
+                up("worst_of_bar", v)
+            elif k.endswith("worst_u"):
+                up("worst_u", v)
+            elif k.endswith("mismatches"):
+                out["mismatches"] += int(v)
+            elif k in ("bce_worst", "dlog_worst"):
+                up("bce_dlog_worst_abs", v)
+    return out
+
+
 def assemble(src, parent_commit, date):
     """Build profiles/gemm_errors.json from the files a GPU run of
-    tests/test_gpu_gemm_routes.py left in ``src`` (ABCD_PARITY_DUMP=<src>)."""
-    rows = []
+    tests/test_gpu_gemm_routes.py and tests/test_gpu_wgrad_offset.py left in
+    ``src`` (ABCD_PARITY_DUMP=<src>)."""
+    rows, extra = [], OrderedDict((s, []) for s in SECTIONS)
     for path in sorted(glob.glob(os.path.join(src, "gemm_*.json"))):
         with open(path) as f:
-            rows.append(json.load(f))
+            r = json.load(f)
+        sec = [s for s, entries in SECTIONS.items() if r.get("entry") in entries]
+        (extra[sec[0]] if sec else rows).append(r)
     routes = sorted({r["route"] for r in rows if r.get("route")})
     worst = dict(
         a_worst_of_bar=max((k["worst_of_bar"] for r in rows for k in r.get("kinds", {}).values()
@@ -442,13 +486,19 @@ def assemble(src, parent_commit, date):
         maxnorm_worst_of_e32=max((k["e_maxnorm"] / k["e32"] for r in rows for k in r.get("kinds", {}).values()
                                   if k.get("e32")), default=None),
         b_mismatches=sum(k.get("mismatches", 0) for r in rows for k in r.get("kinds", {}).values()))
-    doc = dict(what="figures observed by tests/test_gpu_gemm_routes.py (ABCD_PARITY_DUMP) on one MI355X; data kinds "
+    doc = dict(what="figures observed by tests/test_gpu_gemm_routes.py (cases, worst, routes_seen) and "
+                    "tests/test_gpu_wgrad_offset.py (the sections lstm_wgrad, offset_head, tn_batch, colsum_batch, each "
+                    "with its own worst) in one run (ABCD_PARITY_DUMP) on one MI355X; data kinds "
                     "and bars: tests/gemm_cases.py.  worst_of_bar: max |C - ref| / (2 max(K, 16) u S); worst_u: max "
                     "|C - ref| / (u |ref|) on single-product data (bar 8); e_maxnorm / e32: max-norm relative errors "
                     "of the library and of torch's fp32 GEMM (bar 4 e32 + 1e-7); mismatches: outputs of the "
                     "power-of-two selection data that differ from the exact product in any bit (bar 0)",
                date=date, parent_commit=parent_commit, worst=worst, routes_seen=routes,
                routes_expected_missing=[r for r in ROUTES_EXPECTED if r not in routes], cases=rows)
+    for s, rs in extra.items():   # tests/test_gpu_wgrad_offset.py (tables and bars: tests/wgrad_cases.py)
+        # routes_seen: dispatch records / route strings the tests read back and asserted (colsum_batch has one
+        # form and records none)
+        doc[s] = dict(worst=section_worst(rs), routes_seen=sorted({r["route"] for r in rs if r.get("route")}), cases=rs)
     out = os.path.join(REPO, "profiles", "gemm_errors.json")
     with open(out, "w") as f:
         json.dump(doc, f, indent=1)

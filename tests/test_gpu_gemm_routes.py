@@ -14,8 +14,8 @@ Every observed figure is kept with ``ABCD_PARITY_DUMP``
 
 Not reached here (operands >= 2 GiB): ``gemm_x6s<4,4,kc,kc>`` and the
 non-buffer fallback of the K-major path (``x6s<4,4>``).  gemm_wg2 / gemm_wg3b,
-the offset-head modes of gemm_x6r8 and gemm_tn_batch are held by their owners'
-tests."""
+the offset-head modes of gemm_x6r8, gemm_tn_batch and colsum_batch are pinned
+the same way by tests/test_gpu_wgrad_offset.py (tables: tests/wgrad_cases.py)."""
 import pytest
 import torch
 
