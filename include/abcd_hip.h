@@ -951,6 +951,118 @@ int abcd_warp_path(const abcd_packed* x, const float* gt_offset, int P, int T_pr
                    float* path_off, float* path_move, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Time-warped segmentation: the recording is cut with the
+ * prototypes warped inside the dynamic programme.  The state is (category k,
+ * prototype step s); inside a category the moves are those of abcd_warp_nll
+ * (stay, step, skip, log_move a HOST array of three doubles, -inf disables a
+ * move); leaving a category's lattice ends a segment and pays the end-of-segment
+ * logit; entering the next one pays abcd_span_chain_viterbi's transition.  x is
+ * the recording (N x F, row stride ld_x), the prototypes are the rectangle of
+ * abcd_pairwise_nll (T = T_proto steps, K prototypes, row r = s K + k), v[s,k]
+ * = proto_offset_logits[s K + k], log_enter[k] floats (NULL: 0), gap,
+ * seg_bonus, log_trans, log_init those of abcd_span_chain_viterbi, s_min the
+ * lowest state a segment may end in.  In fp64 after widening, every addition as
+ * written, sp(u) = max(u,0) + log1p(e^-|u|):
+ *   e(n,k,s)  = 0.5 sum_f (log 2pi + lv[s,k,f] + (x[n,f] - mu[s,k,f])^2 e^-lv[s,k,f])
+ *               (fp32, the column order of abcd_pairwise_nll)
+ *   cont[k,s] = sp(v[s,k])     last[k,s] = sp(-v[s,k])
+ *   G[0] = 0, G[n] = G[n-1] + gap[n-1]          (gap NULL: -inf for n >= 1)
+ *   W[0][k] = -inf,  H[-1][k][s] = -inf
+ *   for frame n = 0 .. N-1:
+ *     U[n][k]    = max(G[n] + log_init[k], max_k' (W[n][k'] + log_trans[k' ld_trans + k]))
+ *     A[n][k][0] = max(U[n][k] + log_enter[k], H[n-1][k][0] + log_move[0])
+ *     A[n][k][s] = max_{m in 0..2, s-m >= 0} (H[n-1][k][s-m] + log_move[m])          s >= 1
+ *     H[n][k][s] = (A[n][k][s] - e(n,k,s)) - cont[k,s]                               the segment goes on
+ *     X[n+1][k]  = max_{s >= s_min} ((A[n][k][s] - e(n,k,s)) - last[k,s]) + seg_bonus  it ends with frame n
+ *     W[n+1][k]  = max(W[n][k] + gap[n], X[n+1][k])
+ *   path_score = max(G[N], max_k W[N][k])
+ * NaN and -inf candidates are excluded; a NaN or +inf e excludes its cell (H
+ * = -inf, no ending); +inf anywhere else is outside the contract.  Ties: in A
+ * enter, then stay, step, skip; in X the lowest s; in W the gap against a
+ * segment; in U the initial term, then the lowest k'; at the end "no segment",
+ * then the lowest k.  Every H cell carries the frame at which its segment was
+ * entered; X's winner records that onset and its state per (n + 1, k), W gap or
+ * segment, U its k' (-1: the initial term).  There is no per-cell back-pointer
+ * plane: a segment's state path comes from abcd_warp_path on the cut segment.
+ * The backtrack is abcd_span_chain_viterbi's and runs on the device.  Segments
+ * come out in time order, N entries per buffer, n_segments valid: seg_onset,
+ * seg_length, seg_cat, seg_last_state, seg_enter (the U[onset][k] the segment
+ * was entered from), seg_exit (its X[end][k]) and seg_link (the log_init or
+ * log_trans term, widened).  With the step move alone and log_enter = 0 the
+ * programme is abcd_span_chain_viterbi with D = T_proto and d_min = s_min + 1.
+ *
+ * abcd_frame_costs: cost[(n - n0) ld_cost + r] = e(n, r) in fp32 for n0 <= n <
+ * n1 and every rectangle row r < T K.  The emission tile of abcd_pairwise_nll
+ * with the rectangle's rows as the "prototypes" of one step: 32 frames x 32
+ * rows per 256-thread workgroup over a grid of all the tiles.  A pair's bits
+ * depend on its frame and its row alone, not on n0, the chunk or the tile
+ * position.  No atomics, no device-global word, two calls agree bit for bit.
+ * Rows >= N of x, columns >= F and the padding of every stride are never read;
+ * nothing outside the (n1 - n0) x T K block is written.  ABCD_EINVAL: the
+ * limits below, F < 1, ld_x, ld_mu or ld_lv < F, ld_cost < T K, not 0 <= n0 <
+ * n1 <= N, a NULL pointer.
+ *
+ * abcd_warp_segment_window: frames n0 .. n1 - 1 of the recurrence on such a
+ * plane, whose row 0 is frame n0.  The programme is carried across the calls
+ * in the workspace, which must not be touched between them; in this order,
+ * cells = (N + 1) K and S = K T: U and the chosen X (cells doubles each), W's
+ * choice, the onset, the last state and k' (cells int32 each), cont and last
+ * (S doubles each, formed by the call with n0 = 0), the two H rows (2 S
+ * doubles; H[n] is row n mod 2) with their onsets (2 S int32), W[n1] (K
+ * doubles), G[n1] and the next frame (one 64-bit integer).  Calls go in order
+ * on ONE stream with the same arguments but cost, n0 and n1; n0 = 0 starts
+ * over.  A call whose n0 is not the carried frame runs nothing, writes
+ * path_score = NaN and n_segments = -1 and leaves the carry as it is.  The call
+ * with n1 = N backtracks and writes the outputs.  W_out ((N + 1) x K doubles,
+ * may be NULL) receives rows n0 + 1 .. n1 (row 0 too when n0 = 0).  Any split
+ * of 0 .. N into calls gives the one-call outputs bit for bit.
+ * One workgroup of 1024 threads.  With R = 1024 / K, thread r K + k owns the
+ * states s = r, r + R, ... of category k, as many as K T needs, so consecutive
+ * threads touch consecutive s K + k of H, the plane and the logits.  The H
+ * rows alternate in the workspace (L2); the workgroup reads its own stores a
+ * barrier later.  U splits k' over the same (r, k) grid; log_trans is resident
+ * in LDS up to K = 128 and streamed above (abcd_warp_segment_plan says which,
+ * with the launch width and the LDS bytes; it is a pure function).  The
+ * threads' partial maxima of U and X meet in LDS and thread k joins them in r
+ * order under the tie rules.  No atomics, no device-global word, no workgroup
+ * waits for another; two sequences of calls agree bit for bit.
+ * Limits: 1 <= K <= 1024, 1 <= T_proto <= 16383, K T_proto < 2^24, (N + 1) K <
+ * 2^31, (n1 - n0) ld_cost < 2^31; the queries return 0 beyond them.
+ * ABCD_EINVAL (on the host before any launch, nothing is written): those
+ * limits, ld_cost < K T_proto, ld_trans < K, s_min outside 0 .. T_proto - 1, a
+ * NaN or +inf move, all three moves disabled, anything but 0 <= n0 < n1 <= N, a
+ * NULL among cost, proto_offset_logits, log_move, log_trans, log_init,
+ * path_score, n_segments and the seven segment buffers, a missing or short
+ * workspace.  N = 0 (with n0 = n1 = 0) gives path_score = 0, n_segments = 0 and
+ * W_out[0][k] = -inf (each where not NULL) and reads nothing.
+ *
+ * Measured on one MI355X at N = 15 000, K = 128, T_proto = 200, F = 129
+ * (profiles/warpseg_bench.json): abcd_frame_costs 5.85 ms (0.39
+ * us per frame), abcd_warp_segment_window 787.3 ms on a plane read from HBM
+ * (52.5 us per frame), plane and programme chunk by chunk 690.0 ms (46.0 us per
+ * frame), against abcd_span_table + abcd_span_chain_viterbi at D = 200 on the
+ * same frames, 8.39 + 209.4 ms (13.96 us per step): 3.17 x slower end to end.  The step is bound by
+ * latency, not bandwidth: each thread walks 25 cells per frame and each cell
+ * waits for its loads from L2 (H, onsets, logits) or HBM (the plane) behind
+ * four barriers per frame.  Peak memory 0.33 GB (a 268 MB plane chunk and 62 MB
+ * of state) against the table's 3.07 GB.
+ *
+ * No timing or dispatch id is assigned to these entry points.
+ * ---------------------------------------------------------------------- */
+int abcd_frame_costs(const float* x, long ld_x, long N, long n0, long n1, int F, int K, int T_proto,
+                     const float* proto_mu, long ld_mu, const float* proto_lv, long ld_lv, float* cost, long ld_cost,
+                     void* stream);
+int abcd_warp_segment_plan(int K, int T_proto, int* resident, int* threads, size_t* lds_bytes);
+size_t abcd_warp_segment_workspace_bytes(long N, int K, int T_proto);
+int abcd_warp_segment_window(const float* cost, long ld_cost, long n0, long n1, long N, int K, int T_proto,
+                             const float* proto_offset_logits, const double* log_move, const float* log_enter,
+                             const float* gap, double seg_bonus, const float* log_trans, long ld_trans,
+                             const float* log_init, int s_min, double* path_score, int32_t* n_segments,
+                             int32_t* seg_onset, int32_t* seg_length, int32_t* seg_cat, int32_t* seg_last_state,
+                             double* seg_enter, double* seg_exit, double* seg_link, double* W_out, void* ws,
+                             size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

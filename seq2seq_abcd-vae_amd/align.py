@@ -48,7 +48,7 @@ TABLE = (("length", np.int64), ("category_ix", np.int64), ("category_prob", np.f
          ("n_skip", np.int64))
 PATH_COLUMNS = ("data_ix", "frame", "state")
 PATHS = (("frame", np.int64), ("state", np.int64))
-DEFAULT_MOVES = (0.2, 0.6, 0.2)
+DEFAULT_MOVES = cli.DEFAULT_MOVES
 
 
 class Aligner(classify.Classifier):
@@ -127,9 +127,8 @@ def get_parameters(argv=None):
     cli.add_prior_arguments(
         p, prior_help="log weights of the categories: the Dirichlet posterior's E[log pi_k] (default) or zero",
         size_help="N of the Dirichlet posterior softmax(shape logits) * N + a0 (default: the number of segments)")
-    p.add_argument("--moves", type=float, nargs=3, default=list(DEFAULT_MOVES), metavar=("STAY", "STEP", "SKIP"),
-                   help="probabilities of advancing 0, 1 or 2 prototype steps per frame (normalised; 0 disables a "
-                        "move; 0 1 0 is classify.py's rigid comparison)")
+    cli.add_moves_argument(p, "probabilities of advancing 0, 1 or 2 prototype steps per frame (normalised; 0 disables "
+                              "a move; 0 1 0 is classify.py's rigid comparison)")
     p.add_argument("--band", type=int, default=None, help="only alignments with |step - frame| <= N (default: no band)")
     p.add_argument("--marginal", action="store_true",
                    help="sum over all alignments instead of taking the best one (paths stay the best ones)")
@@ -140,8 +139,7 @@ def get_parameters(argv=None):
     p.add_argument("--paths", type=str, default=None, help="also write one row per frame (data_ix, frame, state) here")
     a = p.parse_args(argv)
     cli.check_prior_arguments(p, a)
-    if any(m < 0 or math.isnan(m) or math.isinf(m) for m in a.moves) or not sum(a.moves) > 0:
-        p.error("--moves: three non-negative weights, not all zero")
+    cli.check_moves_argument(p, a)
     if a.band is not None and a.band < 0:
         p.error("--band must not be negative")
     if not a.proto_factor > 0:

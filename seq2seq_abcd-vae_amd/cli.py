@@ -6,6 +6,7 @@ leave nothing partial behind, and the annotation columns joined to a table.
 ``learning.py`` and ``plain_learning.py`` keep their own parsers: their flags
 and help mirror the reference's trainers."""
 import contextlib
+import math
 import os
 
 import numpy as np
@@ -62,6 +63,19 @@ def add_prior_arguments(p, prior_help, size_help):
 def check_prior_arguments(p, a):
     if a.entire_data_size is not None and not a.entire_data_size > 0:
         p.error("--entire_data_size must be positive")
+
+
+DEFAULT_MOVES = (0.2, 0.6, 0.2)   # stay, step, skip
+
+
+def add_moves_argument(p, moves_help):
+    p.add_argument("--moves", type=float, nargs=3, default=list(DEFAULT_MOVES), metavar=("STAY", "STEP", "SKIP"),
+                   help=moves_help)
+
+
+def check_moves_argument(p, a):
+    if any(m < 0 or math.isnan(m) or math.isinf(m) for m in a.moves) or not sum(a.moves) > 0:
+        p.error("--moves: three non-negative weights, not all zero")
 
 
 def frame_hop(a, fs):

@@ -975,6 +975,28 @@ class RNN_Variational_Decoder(torch.nn.Module):
                                             bool(want_best))
         return (table, score, cat) if want_best else (table, None, None)
 
+    def frame_costs(self, prototypes, frames, steps, n0, n1):
+        """Frames ``n0 .. n1 - 1`` of ``frames`` (N x F) against every one of the
+        first ``steps`` steps of every prototype: ``cost[n - n0, s * P + p]``
+        (float32, ``(n1 - n0) x steps P``), the emission NLL of frame n under
+        step s of prototype p -- the plane the time-warped segmentation
+        programme reads (``ops.warp_segment_window``), ``4 (n1 - n0) steps P``
+        bytes.  An entry does not depend on the chunk it was computed in.
+        Forward-only, under ``torch.no_grad()``."""
+        mu, lv, offl = prototypes
+        N.require_gpu(mu)
+        N.require_gpu(frames)
+        F, T = self.rnn_cell.cell.input_size, int(steps)
+        if not (mu.dim() == 3 and offl.dim() == 2 and tuple(mu.shape) == tuple(lv.shape) == (*offl.shape, F)
+                and offl.shape[0] >= T >= 1):
+            raise ValueError(f"frame_costs: prototypes must be prototypes()'s (mu, log_var, offset_logits), "
+                             f"T_proto x P x {F} / T_proto x P with T_proto >= steps = {T} >= 1")
+        if frames.dim() != 2 or frames.shape[1] != F:
+            raise ValueError(f"frame_costs: frames must be N x {F}, got {tuple(frames.shape)}")
+        with torch.no_grad():
+            return ops.frame_costs(frames.to(mu.device), mu[:T].reshape(-1, F), lv[:T].reshape(-1, F),
+                                   int(offl.shape[1]), int(n0), int(n1))
+
     def _length_to_batch_sizes(self, lengths):
         lengths = torch.as_tensor(lengths).cpu()
         return torch.tensor([int((lengths > t).sum()) for t in range(int(lengths.max()))], dtype=torch.int64)

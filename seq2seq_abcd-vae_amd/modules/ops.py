@@ -37,13 +37,15 @@ operator                   replaces (reference)                            C ent
 ``abcd::span_chain_viterbi`` (none: the best cover under a category chain) ``abcd_span_chain_viterbi``
 ``abcd::span_chain_posterior`` (none: posteriors and counts under the chain) ``abcd_span_chain_posterior``
 ``abcd::span_chain_viterbi_window`` (none: that cover, the table in windows) ``abcd_span_chain_viterbi_window``
+``abcd::frame_costs``      (none: frames against every prototype step)     ``abcd_frame_costs``
+``abcd::warp_segment_window`` (none: the cut with warped prototypes)       ``abcd_warp_segment_window``
 =========================  ==============================================  =========================================
 
-The last sixteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
+The last eighteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
-``span_chain_viterbi_window`` is the one operator that is NOT functional: it
-carries a recording's programme from call to call in a state tensor it mutates
+``span_chain_viterbi_window`` and ``warp_segment_window`` are the operators that are NOT functional: they
+carry a recording's programme from call to call in a state tensor they mutate
 (``STATEFUL_OPS``; ``OPS`` lists the functional ones).
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -1296,6 +1298,15 @@ DEFAULT_LOG_MOVES = (math.log(0.2), math.log(0.6), math.log(0.2))   # stay, step
 IDENTITY_LOG_MOVES = (-math.inf, 0.0, -math.inf)                    # step only: pairwise_nll's comparison
 
 
+def _log_moves_arg(name, log_moves):
+    """Three log weights (stay, step, skip) as the C calls take them (a host array of doubles)."""
+    lm = [float(v) for v in log_moves]
+    if len(lm) != 3 or any(math.isnan(v) or v == math.inf for v in lm) or all(v == -math.inf for v in lm):
+        raise ValueError(f"{name}: log_moves must be three log weights (stay, step, skip), -inf to disable a move, "
+                         f"at least one enabled; got {lm}")
+    return (N.c_double * 3)(*lm)
+
+
 def _warp_args(name, gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offset_logits, log_moves, band, P, F):
     """The argument checks warp_nll and warp_path share -> the C call's inputs."""
     for t in (gt, gt_offset, proto_mu, proto_lv, proto_offset_logits):
@@ -1303,10 +1314,7 @@ def _warp_args(name, gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offse
     P, F = int(P), int(F)
     if P < 1:
         raise ValueError(f"{name}: P must be at least 1")
-    lm = [float(v) for v in log_moves]
-    if len(lm) != 3 or any(math.isnan(v) or v == math.inf for v in lm) or all(v == -math.inf for v in lm):
-        raise ValueError(f"{name}: log_moves must be three log weights (stay, step, skip), -inf to disable a move, "
-                         f"at least one enabled; got {lm}")
+    moves = _log_moves_arg(name, log_moves)
     gt = gt.contiguous()
     (mu, ldm), (lv, ldl) = _rows(proto_mu), _rows(proto_lv)
     ol = proto_offset_logits.contiguous()
@@ -1319,7 +1327,6 @@ def _warp_args(name, gt, batch_sizes, gt_offset, proto_mu, proto_lv, proto_offse
         raise ValueError(f"{name}: gt must be {(pk.L, F)}, proto_mu and proto_lv {(rows, F)}")
     if not (gt_offset.numel() == pk.L and ol.numel() == rows):
         raise ValueError(f"{name}: gt_offset must hold {pk.L} entries, proto_offset_logits {rows}")
-    moves = (N.c_double * 3)(*lm)
     return pk, bs, gt, gt_offset, mu, ldm, lv, ldl, ol, rows // P, moves, int(band)
 
 
@@ -1399,6 +1406,138 @@ _forward_only(warp_path, "warp_path")
 
 
 # ----------------------------------------------------------------------------
+# time-warped segmentation: prototypes warped inside the cut (forward-only)
+# ----------------------------------------------------------------------------
+_WARPSEG_LIMIT = "K > 1024, T_proto > 16383, K * T_proto >= 2^24 or (N + 1) * K >= 2^31"
+
+
+@torch.library.custom_op("abcd::frame_costs", mutates_args=())
+def frame_costs(frames: Tensor, proto_mu: Tensor, proto_lv: Tensor, K: int, n0: int, n1: int) -> Tensor:
+    """-> cost ((n1 - n0) x T_proto K, fp32): the emission NLL of frames n0 ..
+    n1 - 1 (of N x F, row-strided views pass without a copy) under every row r
+    = s K + k of the prototype rectangle of pairwise_nll (abcd_frame_costs).
+    An entry's bits depend on its frame and its row alone, so the plane may be
+    built in chunks."""
+    for t in (frames, proto_mu, proto_lv):
+        N.require_gpu(t)
+    K, n0, n1 = int(K), int(n0), int(n1)
+    if frames.dim() != 2 or frames.shape[1] < 1:
+        raise ValueError(f"frame_costs: frames must be N x F, got {tuple(frames.shape)}")
+    n, F = (int(v) for v in frames.shape)
+    if not 0 <= n0 < n1 <= n:
+        raise ValueError(f"frame_costs: 0 <= n0 < n1 <= N, got {n0}, {n1} and N = {n}")
+    (x, ldx), (mu, ldm), (lv, ldl) = _rows(frames.float()), _rows(proto_mu.float()), _rows(proto_lv.float())
+    rows = int(mu.shape[0]) if mu.dim() == 2 else 0
+    if K < 1 or rows < K or rows % K or not (tuple(mu.shape) == tuple(lv.shape) == (rows, F)):
+        raise ValueError(f"frame_costs: proto_mu and proto_lv must be T_proto * {K} x {F} with T_proto >= 1, got "
+                         f"{tuple(proto_mu.shape)} and {tuple(proto_lv.shape)}")
+    L_ = N.lib()
+    if L_.abcd_warp_segment_workspace_bytes(n, K, rows // K) == 0 or (n1 - n0) * rows >= 2 ** 31:
+        raise N.HipError(f"frame_costs: unsupported shape ({_WARPSEG_LIMIT}, or (n1 - n0) * K * T_proto >= 2^31); "
+                         f"N = {n}, K = {K}, T_proto = {rows // K}")
+    cost = torch.empty(n1 - n0, rows, device=frames.device)
+    N.check(L_.abcd_frame_costs(N.ptr(x), ldx, n, n0, n1, F, K, rows // K, N.ptr(mu), ldm, N.ptr(lv), ldl,
+                                N.ptr(cost), rows, N.stream()), "frame costs")
+    return cost
+
+
+@frame_costs.register_fake
+def _(frames, proto_mu, proto_lv, K, n0, n1):
+    return frames.new_empty(int(n1) - int(n0), proto_mu.shape[0], dtype=torch.float32)
+
+
+_forward_only(frame_costs, "frame_costs")
+
+
+def warp_segment_state(n, K, T, device=None):
+    """The state tensor ``warp_segment_window`` carries a recording of ``n``
+    frames in (uint8; abcd_warp_segment_workspace_bytes: 32 (n + 1) K + 40 K T
+    bytes and a little).  In this order, with cells = (n + 1) K and S = K T: U
+    and the chosen X (cells fp64 each), W's choice, the onset, the last state
+    and k' (cells int32 each), sp(v) and sp(-v) (S fp64 each), the two H rows
+    (2 S fp64) with their onsets (2 S int32), W (K fp64), G, the next frame."""
+    nbytes = N.lib().abcd_warp_segment_workspace_bytes(int(n), int(K), int(T))
+    if nbytes == 0:
+        raise N.HipError(f"warp_segment_window: unsupported shape ({_WARPSEG_LIMIT}); N = {n}, K = {K}, T_proto = {T}")
+    return N.workspace(nbytes, device if device is not None else torch.device("cuda"))
+
+
+@torch.library.custom_op("abcd::warp_segment_window", mutates_args=("state", "W"))
+def warp_segment_window(cost: Tensor, n0: int, n1: int, n: int, K: int, proto_offset_logits: Tensor,
+                        log_moves: List[float], log_enter: Optional[Tensor], gap: Optional[Tensor],
+                        seg_bonus: float, log_trans: Tensor, log_init: Tensor, s_min: int, state: Tensor,
+                        W: Optional[Tensor]) -> List[Tensor]:
+    """Frames n0 .. n1 - 1 of the time-warped segmentation programme over a
+    recording of n frames on frame_costs' plane of those frames (row 0 is frame
+    n0; more rows may follow), the programme being carried from call to call in
+    ``state`` (warp_segment_state; mutated) and, when given, rows n0 + 1 .. n1 of
+    W ((n + 1) x K fp64; mutated; row 0 too at n0 = 0) being written
+    (abcd_warp_segment_window).  The calls of a recording run in order on one
+    stream: n0 = 0 first, then every n0 the previous n1.  -> [path_score (0-d,
+    fp64), n_segments (0-d, int32), onset, length, category, last_state (n
+    each, int32), enter, exit, link (n each, fp64)], written by the call with
+    n1 = n; before that, and after a call out of order, path_score is NaN and
+    n_segments -1.  gap holds the n scores of the whole recording."""
+    for t in (cost, proto_offset_logits, log_trans, log_init):
+        N.require_gpu(t)
+    n0, n1, n, K, s_min = int(n0), int(n1), int(n), int(K), int(s_min)
+    moves = _log_moves_arg("warp_segment_window", log_moves)
+    ol = proto_offset_logits.float().contiguous()
+    S = int(ol.numel())
+    if K < 1 or S < K or S % K:
+        raise ValueError(f"warp_segment_window: proto_offset_logits must hold T_proto * {K} entries, got {S}")
+    T = S // K
+    if K > 1024:
+        raise ValueError(f"warp_segment_window: at most 1024 categories, got {K}")
+    if not 0 <= n0 < n1 <= n:
+        raise ValueError(f"warp_segment_window: 0 <= n0 < n1 <= N, got {n0}, {n1} and N = {n}")
+    if cost.dim() != 2 or cost.shape[0] < n1 - n0 or cost.shape[1] != S:
+        raise ValueError(f"warp_segment_window: cost must hold at least {n1 - n0} rows of {S}, got {tuple(cost.shape)}")
+    if not 0 <= s_min < T:
+        raise ValueError(f"warp_segment_window: s_min must lie in 0 .. {T - 1}, got {s_min}")
+    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
+        raise ValueError(f"warp_segment_window: log_trans must be {K} x {K} and log_init hold {K} entries, got "
+                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
+    le = None
+    if log_enter is not None:
+        N.require_gpu(log_enter)
+        if log_enter.numel() != K:
+            raise ValueError(f"warp_segment_window: log_enter must hold {K} entries, got {log_enter.numel()}")
+        le = log_enter.float().contiguous()
+    c, ldc = _rows(cost.float())
+    lt, ldt = _rows(log_trans.float())
+    li = log_init.float().contiguous()
+    g = _gap_arg("warp_segment_window", gap, n)
+    L_ = N.lib()
+    nbytes = L_.abcd_warp_segment_workspace_bytes(n, K, T)
+    N.require_gpu(state)
+    if nbytes == 0 or state.dtype != torch.uint8 or not state.is_contiguous() or state.numel() < nbytes:
+        raise ValueError(f"warp_segment_window: state must be warp_segment_state({n}, {K}, {T})")
+    if W is not None:
+        N.require_gpu(W)
+        if tuple(W.shape) != (n + 1, K) or W.dtype != torch.float64 or not W.is_contiguous():
+            raise ValueError(f"warp_segment_window: W must be {(n + 1, K)} contiguous float64")
+    dev = cost.device
+    i32, f64 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float64, device=dev)
+    outs = ([torch.full((), float("nan"), **f64), torch.full((), -1, **i32)] +
+            [torch.zeros(n, **i32) for _ in range(4)] + [torch.zeros(n, **f64) for _ in range(3)])
+    N.check(L_.abcd_warp_segment_window(N.ptr(c), ldc, n0, n1, n, K, T, N.ptr(ol), moves, N.ptr(le), N.ptr(g),
+                                        float(seg_bonus), N.ptr(lt), ldt, N.ptr(li), s_min,
+                                        *(N.ptr(t) for t in outs), N.ptr(W), N.ptr(state), state.numel(), N.stream()),
+            "warp segment window")
+    return outs
+
+
+@warp_segment_window.register_fake
+def _(cost, n0, n1, n, K, proto_offset_logits, log_moves, log_enter, gap, seg_bonus, log_trans, log_init, s_min,
+      state, W):
+    n = int(n)
+    e = cost.new_empty
+    return ([e((), dtype=torch.float64), e((), dtype=torch.int32)] + [e(n, dtype=torch.int32) for _ in range(4)] +
+            [e(n, dtype=torch.float64) for _ in range(3)])
+
+
+# ----------------------------------------------------------------------------
 # log-spectra back to audio (forward-only)
 # ----------------------------------------------------------------------------
 @torch.library.custom_op("abcd::griffin_lim", mutates_args=())
@@ -1454,8 +1593,8 @@ OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sa
        "sampler_kl_bwd", "decoder", "decoder_bwd", "linear", "linear_bwd", "segment_losses", "sampler_kl_rows",
        "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
        "warp_nll", "warp_path", "span_evidence", "span_posterior", "span_table", "span_chain_viterbi",
-       "span_chain_posterior")
-STATEFUL_OPS = ("span_chain_viterbi_window",)  # mutate a state argument: kept apart from the functional OPS
+       "span_chain_posterior", "frame_costs")
+STATEFUL_OPS = ("span_chain_viterbi_window", "warp_segment_window")  # mutate a state argument: kept apart from the functional OPS
 
 
 def registered() -> Sequence[str]:

@@ -249,6 +249,90 @@ def _chain_dict(ps, k, onset, length, category, seg, link, v, lw, include_weight
             "path_score": ps, "link": link[:k], "context_free_category": free.to(torch.int64)}
 
 
+PLANE_BUDGET_BYTES = 256 << 20  # segment_frames_warped's default chunk keeps the emission plane under this
+
+
+def default_chunk_frames(steps, K, budget=PLANE_BUDGET_BYTES):
+    """The frames per chunk that keep ``4 chunk_frames steps K`` bytes under ``budget`` (at least 1).  A pure function."""
+    return max(1, int(budget) // (4 * int(steps) * int(K)))
+
+
+def segment_frames_warped(decoder, prototypes, frames, steps, log_moves=ops.DEFAULT_LOG_MOVES, transitions=None,
+                          log_weight=None, gap=None, seg_bonus=0.0, min_state=0, chunk_frames=None,
+                          include_weight=False):
+    """``segment_frames`` with the prototypes time-warped INSIDE the cut: the
+    state of the dynamic programme is (category, prototype step), a frame stays
+    on its step, moves to the next or skips one at ``log_moves`` (stay, step,
+    skip; -inf disables a move), a segment ends in a step ``>= min_state`` and
+    pays that step's end-of-segment logit, and the next one pays the
+    transition (``ops.warp_segment_window``).  ``steps`` is
+    how many of the prototypes' steps are states.  The programme costs ``N K
+    steps`` cell updates, whatever the segments' lengths.
+
+    The emission plane is built ``chunk_frames`` frames at a time
+    (``decoder.frame_costs``), run and freed: peak plane memory is ``4
+    chunk_frames steps K`` bytes whatever N (None: ``default_chunk_frames``,
+    under ``PLANE_BUDGET_BYTES`` = 256 MiB); the carried state takes ``32 (N +
+    1) K + 40 K steps`` bytes.  The result does not depend on ``chunk_frames``.
+
+    ``transitions=None`` is a zero matrix and a zero initial vector with
+    ``log_weight`` as the price of entering a category; with ``transitions``
+    ``log_weight`` is used only under ``include_weight``, as in
+    ``segment_frames``.  Returns ``segment_frames``' dict: ``onset``,
+    ``length``, ``category`` (int64), ``link``, ``path_score`` and ``score``
+    (float64: what the segment adds to the path between entering and leaving
+    it, its log weight, emissions, end-of-segment logits and moves), and
+    ``last_state`` (int64: the step the segment ends in) and ``tempo`` (float64:
+    ``(last_state + 1) / length``, prototype steps per frame)."""
+    # the plain arguments first: their errors need no device
+    mu, lv, offl = prototypes
+    T, s_min = int(steps), int(min_state)
+    if offl.dim() != 2 or not 1 <= T <= int(offl.shape[0]):
+        raise ValueError(f"segment_frames_warped: 1 <= steps <= the prototypes' {int(offl.shape[0])} steps, got {T}")
+    if not 0 <= s_min < T:
+        raise ValueError(f"segment_frames_warped: min_state must lie in 0 .. {T - 1}, got {s_min}")
+    K = int(offl.shape[1])
+    chunk = default_chunk_frames(T, K) if chunk_frames is None else int(chunk_frames)
+    if chunk < 1:
+        raise ValueError(f"segment_frames_warped: chunk_frames must be at least 1, got {chunk_frames}")
+    lm = list(ops._log_moves_arg("segment_frames_warped", log_moves))
+    if log_weight is not None and torch.as_tensor(log_weight).numel() != K:
+        raise ValueError(f"segment_frames_warped: log_weight must hold {K} entries, got "
+                         f"{torch.as_tensor(log_weight).numel()}")
+    N.require_gpu(frames)
+    n = int(frames.shape[0])
+    dev = frames.device
+    lw = None if log_weight is None else torch.as_tensor(log_weight, device=dev).float().reshape(-1)
+    if transitions is None:
+        lt, li, le = torch.zeros(K, K, device=dev), torch.zeros(K, device=dev), lw
+    else:
+        lt, li, _ = _chain_setup("segment_frames_warped", transitions, prototypes, dev)
+        le = lw if include_weight else None
+    i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
+    if n == 0:
+        return {"onset": torch.zeros(0, **i64), "length": torch.zeros(0, **i64), "category": torch.zeros(0, **i64),
+                "score": torch.zeros(0, **f64), "path_score": torch.zeros((), **f64), "link": torch.zeros(0, **f64),
+                "last_state": torch.zeros(0, **i64), "tempo": torch.zeros(0, **f64)}
+    with torch.no_grad():
+        g = None if gap is None else torch.as_tensor(gap, device=dev).float()
+        v = offl[:T].reshape(-1)
+        state = ops.warp_segment_state(n, K, T, dev)
+        for n0 in range(0, n, chunk):
+            n1 = min(n, n0 + chunk)
+            cost = decoder.frame_costs(prototypes, frames, T, n0, n1)
+            ps, ns, onset, length, category, last, enter, exit_, link = ops.warp_segment_window(
+                cost, n0, n1, n, K, v, lm, le, g, float(seg_bonus), lt, li, s_min, state, None)
+            del cost
+        k = int(ns)
+        if k < 0:
+            raise RuntimeError("segment_frames_warped: the chunks of the programme ran out of order")
+        length = length[:k].to(torch.int64)
+        last = last[:k].to(torch.int64)
+        return {"onset": onset[:k].to(torch.int64), "length": length, "category": category[:k].to(torch.int64),
+                "score": exit_[:k] - enter[:k] - float(seg_bonus), "path_score": ps, "link": link[:k],
+                "last_state": last, "tempo": (last + 1).double() / length.double()}
+
+
 def count_transitions(categories_per_recording, K):
     """``(trans_counts K x K, init_counts K)`` in float64 on the CPU:
     ``trans_counts[i, j]`` is how often a segment of category j follows one of

@@ -46,7 +46,15 @@ and appends ``onset_posterior``, ``offset_posterior``, ``span_posterior`` and
 ``label_posterior``: how far to trust each cut and each label.
 ``--window_frames W`` (with ``--transitions``) cuts long recordings' tables into
 windows of W ends: the same segments, bit for bit, at a table memory that does
-not grow with the recording."""
+not grow with the recording.
+
+``--warp`` cuts with the prototypes time-warped inside the dynamic programme
+(``segmentation.segment_frames_warped``): a frame stays on its prototype step,
+moves to the next or skips one with the probabilities ``--moves``, so a segment
+sung slower or faster than its prototype is still one segment.  ``--max_length``
+is then the number of prototype steps, not a bound on the segments' frames; the
+table gains ``last_state`` and ``tempo`` (prototype steps per frame), and
+``transition_score`` with ``--transitions``."""
 import os
 import sys
 
@@ -57,12 +65,13 @@ import torch
 
 import classify
 import cli
-from modules import _native, segmentation
+from modules import _native, alignment, segmentation
 
 COLUMNS = ("onset", "offset", "input_path", "data_type", "speaker", "label", "category_ix", "length", "segment_score")
 POSTERIOR_COLUMNS = ("onset_posterior", "offset_posterior", "span_posterior")   # appended by --posteriors
 SYNTAX_COLUMNS = ("transition_score", "context_free_category_ix", "changed")      # appended by --transitions
 CHAIN_POSTERIOR_COLUMNS = POSTERIOR_COLUMNS + ("label_posterior",)                # appended by --chain_posteriors
+WARP_COLUMNS = ("last_state", "tempo")                                            # appended by --warp
 REFIT_METHODS = ("viterbi", "em")
 TRANSITION_COLUMNS = ("from_ix", "to_ix", "probability", "expected_count")       # sequence.py's transitions.csv
 RECORDING_COLUMNS = ("input_path", "n_frames", "n_segments", "path_score", "log_evidence", "expected_segments")
@@ -111,11 +120,13 @@ def covered_frames(n_frames, onsets, offsets, fs, frame, hop, centering=True):
 
 
 def segment_rows(input_path, onset, length, category, score, fs, frame, hop, centering, total, data_type="segmented",
-                 speaker=float("nan"), posteriors=None, syntax=None, chain_posteriors=None):
+                 speaker=float("nan"), posteriors=None, syntax=None, chain_posteriors=None, warp=None):
     """The table rows of one recording's segments (frame units -> seconds);
     ``posteriors``: the three per-segment lists of POSTERIOR_COLUMNS;
     ``syntax``: (link, context-free category) per segment for SYNTAX_COLUMNS;
-    ``chain_posteriors``: the four per-segment lists of CHAIN_POSTERIOR_COLUMNS."""
+    ``chain_posteriors``: the four per-segment lists of CHAIN_POSTERIOR_COLUMNS;
+    ``warp``: (last state, tempo, link or None) per segment for WARP_COLUMNS
+    and, with a link, ``transition_score``."""
     rows = []
     for i, (s, d, k, v) in enumerate(zip(onset, length, category, score)):
         on, off = frames_to_samples(s, d, frame, hop, centering, total)
@@ -130,20 +141,28 @@ def segment_rows(input_path, onset, length, category, score, fs, frame, hop, cen
                              "changed": int(int(free[i]) != int(k))})
         if chain_posteriors is not None:
             rows[-1].update({c: float(p[i]) for c, p in zip(CHAIN_POSTERIOR_COLUMNS, chain_posteriors)})
+        if warp is not None:
+            last, tempo, link = warp
+            rows[-1].update({"last_state": int(last[i]), "tempo": float(tempo[i])})
+            if link is not None:
+                rows[-1]["transition_score"] = float(link[i])
     return rows
 
 
 def write_segments(save_path, rows, posteriors=False, recordings_out=None, recordings=(), curves=None, syntax=False,
-                   transitions_out=None, transitions=None, chain_posteriors=False):
+                   transitions_out=None, transitions=None, chain_posteriors=False, warp=False):
     """Writes the annotation table (an existing file is kept as .prev, nothing
     partial is left behind) and, with ``posteriors``, its three extra columns,
     the per-recording table and the per-recording curve files ({path: dict of
     arrays}) in the same replacement; with ``syntax`` the SYNTAX_COLUMNS, and
     ``transitions`` (a table in TRANSITION_COLUMNS) to ``transitions_out``;
-    with ``chain_posteriors`` the CHAIN_POSTERIOR_COLUMNS after those.
+    with ``chain_posteriors`` the CHAIN_POSTERIOR_COLUMNS after those; with
+    ``warp`` the WARP_COLUMNS (and, with ``syntax``, ``transition_score`` alone
+    of the SYNTAX_COLUMNS: the warped programme has no context-free label).
     Returns the number of rows."""
     df = pd.DataFrame(rows, columns=list(COLUMNS) + (list(POSTERIOR_COLUMNS) if posteriors else []) +
-                      (list(SYNTAX_COLUMNS) if syntax else []) +
+                      (list(WARP_COLUMNS) if warp else []) +
+                      (list(SYNTAX_COLUMNS[:1] if warp else SYNTAX_COLUMNS) if syntax else []) +
                       (list(CHAIN_POSTERIOR_COLUMNS) if chain_posteriors else []))
     with cli.replacing_outputs() as tmp:
         df.to_csv(tmp(save_path), index=False)
@@ -191,6 +210,18 @@ class Segmenter(classify.Classifier):
         return segmentation.segment_frames(self.decoder, protos, frames.to(self.device), max_length,
                                            min_length=min_length, log_weight=log_weight, gap=gap, seg_bonus=seg_bonus,
                                            **extra)
+
+    def segment_recording_warped(self, frames, steps, log_moves, min_state=0, log_weight=None, gap=None,
+                                 seg_bonus=0.0, speaker=None, transitions=None, chunk_frames=None):
+        """``segmentation.segment_frames_warped`` of one recording's frames under
+        the categories' prototypes decoded for ``steps`` steps."""
+        if self.decoder.embed_speaker is not None and speaker is None:
+            raise ValueError("this decoder embeds speakers: a speaker index is required")
+        protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(steps))
+        return segmentation.segment_frames_warped(self.decoder, protos, frames.to(self.device), int(steps),
+                                                  log_moves=log_moves, transitions=transitions, log_weight=log_weight,
+                                                  gap=gap, seg_bonus=seg_bonus, min_state=min_state,
+                                                  chunk_frames=chunk_frames)
 
     def chain_posteriors(self, frames, max_length, transitions, min_length=1, log_weight=None, gap=None,
                          seg_bonus=0.0, speaker=None, **kw):
@@ -269,7 +300,33 @@ def get_parameters(argv=None):
                         "max_length K < 2^31) does not fit; the same segments bit for bit at a peak table memory of at "
                         "most 8 (W + max_length + 32) max_length K bytes whatever the recording's length; 1024 is a "
                         "good value")
+    p.add_argument("--warp", action="store_true",
+                   help="time-warp the prototypes inside the dynamic programme: --max_length is then the number of "
+                        "prototype steps, and a segment may be shorter or longer than that; appends last_state and "
+                        "tempo")
+    cli.add_moves_argument(p, "with --warp: probabilities of advancing 0, 1 or 2 prototype steps per frame "
+                              "(normalised; 0 disables a move; 0 1 0 is the rigid programme)")
+    p.add_argument("--min_state", type=int, default=0,
+                   help="with --warp: the lowest prototype step a segment may end in (raised so that every segment "
+                        "has the frames the loader needs)")
+    p.add_argument("--chunk_frames", type=int, default=None,
+                   help="with --warp: frames of the emission plane built at a time, 4 chunk_frames max_length K bytes "
+                        "(default: as many as fit 256 MiB); the result does not depend on it")
     a = p.parse_args(argv)
+    cli.check_moves_argument(p, a)
+    if a.warp:
+        for flag, on in (("--posteriors", a.posteriors), ("--chain_posteriors", a.chain_posteriors),
+                         ("--window_frames", a.window_frames is not None),
+                         ("--refit_transitions", a.refit_transitions > 0)):
+            if on:
+                p.error(f"--warp cannot be combined with {flag}: the time-warped programme gives the best cut only "
+                        "and needs no table in windows")
+        if not 0 <= a.min_state < a.max_length:
+            p.error("--min_state must lie in 0 .. --max_length - 1")
+        if a.chunk_frames is not None and a.chunk_frames < 1:
+            p.error("--chunk_frames must be at least 1")
+    elif a.min_state != 0 or a.chunk_frames is not None or list(a.moves) != list(cli.DEFAULT_MOVES):
+        p.error("--moves, --min_state and --chunk_frames need --warp")
     if a.window_frames is not None:
         if a.window_frames < 1:
             p.error("--window_frames must be at least 1")
@@ -352,7 +409,7 @@ def main(argv=None):
 
     lw = seg.log_weight(a.prior, len(table) if a.entire_data_size is None else a.entire_data_size)
     syntax = a.transitions is not None or a.refit_transitions > 0
-    model, trans_table, prepared = None, None, {}
+    model, trans_table, prepared, warned = None, None, {}, []
 
     def prepare(path):
         if path in prepared:
@@ -376,6 +433,20 @@ def main(argv=None):
 
     def cut(path, transitions=None, got=None):
         _, _, _, _, frames, d_min, gap = got or prepare(path)
+        if a.warp:
+            # a segment that ends in state s has at least s / (the largest advance) + 1 frames
+            stride = 2 if a.moves[2] > 0 else 1
+            s_min = max(a.min_state, stride * (d_min - 1))
+            if s_min > a.min_state and not warned:
+                warned.append(s_min)
+                print(f"--min_state raised from {a.min_state} to {s_min}: every segment then has the {d_min} frames "
+                      "the loader can featurise", file=sys.stderr)
+            if s_min >= a.max_length:
+                raise SystemExit(f"{path}: --max_length {a.max_length} leaves no state >= {s_min} to end in")
+            return seg.segment_recording_warped(frames, a.max_length, alignment.moves_from_probabilities(a.moves),
+                                                min_state=s_min, log_weight=lw, gap=gap, seg_bonus=a.segment_bonus,
+                                                speaker=a.speaker, transitions=transitions,
+                                                chunk_frames=a.chunk_frames)
         return seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
                                      seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
                                      temperature=a.posterior_temperature, transitions=transitions,
@@ -430,7 +501,10 @@ def main(argv=None):
                              out["score"].tolist(), fs, frame, hop, centering, total, data_type=data_type,
                              speaker=speaker,
                              posteriors=[out[c].tolist() for c in POSTERIOR_COLUMNS] if a.posteriors else None,
-                             syntax=(out["link"].tolist(), out["context_free_category"].tolist()) if syntax else None,
+                             syntax=(out["link"].tolist(), out["context_free_category"].tolist())
+                             if syntax and not a.warp else None,
+                             warp=(out["last_state"].tolist(), out["tempo"].tolist(),
+                                   out["link"].tolist() if syntax else None) if a.warp else None,
                              chain_posteriors=None if post is None else [
                                  post["onset"][out["onset"]].tolist(),
                                  post["end"][out["onset"] + out["length"]].tolist(),
@@ -456,7 +530,7 @@ def main(argv=None):
     _native.op_status.sync("segment")
     write_segments(save_path, rows, posteriors=a.posteriors, recordings_out=a.recordings_out, recordings=recordings,
                    curves=curves, syntax=syntax, transitions_out=a.transitions_out, transitions=trans_table,
-                   chain_posteriors=a.chain_posteriors)
+                   chain_posteriors=a.chain_posteriors, warp=a.warp)
     return save_path
 
 
