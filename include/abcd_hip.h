@@ -1212,6 +1212,13 @@ int abcd_timing_read_kernel(int kid, double* out);
 const char* abcd_dispatch_name(int kid);
 long abcd_dispatch_count(int kid);
 void abcd_dispatch_reset(void);
+/* how that launch dealt its 16-row blocks to the row groups (persistent
+ * recurrent kernels, ids 1 .. 4): 1 cyclic (block j of group g is packed block
+ * g + groups * j), 0 contiguous (also every launch without a deal: per-step
+ * kernels, the other ids); -1: no launch of the role since the reset, or an id
+ * outside the table.  Environment ABCD_PERSIST_DEAL (read per call): a mask of
+ * 1 enc fwd, 2 enc bwd, 4 dec fwd, 8 dec bwd that deal cyclically; 0: none. */
+int abcd_dispatch_deal(int kid);
 /* diagnostics (scripts/, not part of the reference's interface):
  * abcd_debug_persist_prof -- the persistent kernels of the roles in `mask`
  * (1 enc fwd, 2 enc bwd, 4 dec fwd, 8 dec bwd) stamp s_memrealtime at their

@@ -5,6 +5,9 @@ Runs the bench.py c2 workload, enables the s_memtime stamps of one persistent
 kernel at a time (abcd_debug_persist_prof), and prints, per kernel, the median
 over workgroups of each phase's cycles averaged over the time steps, plus
 the kernel's event-timed duration (to convert cycles to microseconds).
+Each kernel's step wall time is also reported by the number of live 16-row
+blocks its workgroup's group holds at that step (the deal of
+blocks to groups decides how long the critical group keeps a full tile).
 
     python scripts/persist_stamps.py [config]      (default c2; e.g. c5)
 """
@@ -24,6 +27,31 @@ NAMES = {1: ("enc_fwd", ["gxload+wait", "mma", "cell+st", "publish+stash"]),
          2: ("enc_bwd", ["epiload+wait+partials", "cell-bwd", "partial-mma+st", "publish"]),
          4: ("dec_fwd", ["cell", "mlp-wait", "mlp", "emit-wait", "emit"]),
          8: ("dec_bwd", ["P0", "P1-wait", "P1", "P2-wait", "P2"])}
+
+
+# the H = 256 forms: rows per group, members, directions, and whether direction 0 walks t downwards
+FORMS = {"enc_fwd": (64, 16, 2, False), "enc_bwd": (32, 8, 2, True), "dec_fwd": (64, 32, 1, False),
+         "dec_bwd": (32, 16, 1, True)}
+
+
+def live_blocks(name, grid, bsz, cyclic):
+    """[workgroup][step i] -> live 16-row blocks of the workgroup's group at the
+    step its iteration i runs (the kernels' group_role and deal_row)."""
+    rows, nmem, nd, down = FORMS[name]
+    T, B = len(bsz), bsz[0]
+    nrt = -(-B // rows)
+    ng, bpg = nd * nrt, rows // 16
+    if ng * nmem != grid:
+        return None
+    out = torch.zeros(grid, T, dtype=torch.int64)
+    for b in range(grid):
+        grp = (b & 7) + 8 * ((b >> 3) // nmem) if ng % 8 == 0 else b // nmem
+        d, rt = grp // nrt, grp % nrt
+        gmul, jstep = (1, nrt) if cyclic else (bpg, 1)
+        for i in range(T):
+            t = T - 1 - i if down != (d == 1) else i  # direction 1 walks the other way
+            out[b, i] = sum(1 for j in range(bpg) if 16 * (rt * gmul + j * jstep) < bsz[t])
+    return out
 
 
 def main():
@@ -81,6 +109,16 @@ def main():
         print(f"   start skew over workgroups: median {float(q[0]):.0f}  p90 {float(q[1]):.0f}  max {float(q[2]):.0f} ns")
         if w.numel():
             print(f"   step wall median {float(w.median()):.0f} ns, mean {float(w.mean()):.0f} ns")
+        cyclic = N.dispatch_deal()[name] == 1
+        live = live_blocks(name, grid, [int(x) for x in b["batch_sizes"]], cyclic)
+        if live is not None:
+            print(f"   step wall by live row blocks of the group ({'cyclic' if cyclic else 'contiguous'} deal):")
+            for n in range(int(live.max()) + 1):
+                sel = okw & (live[:, :-1] == n)
+                if sel.any():
+                    v = wall[sel]
+                    print(f"      {n} blocks: {int(sel.sum())} (wg,step)  median {float(v.median()):.0f} ns  "
+                          f"mean {float(v.mean()):.0f} ns  sum/wg {float(v.sum()) / grid / 1e3:.1f} us")
         # first 40 steps (full batch)
         early = [float(d[:, :40, k][ok[:, :40]].median()) for k in range(nst - 1)]
         print("   first-40-steps: " + "  ".join(f"{p}={c:.0f}" for p, c in zip(phases, early)))

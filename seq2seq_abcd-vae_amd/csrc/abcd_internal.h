@@ -247,6 +247,9 @@ void timing_mark(hipStream_t s, int kid);
 // tests can assert that the production-shape dispatch is the one checked
 // against the reference (abcd_dispatch_name / abcd_dispatch_count)
 void note_dispatch(int kid, const char* fmt, ...);
+// the block deal of the launch just noted (abcd_persist.h: BlockDeal; read
+// back by abcd_dispatch_deal); note_dispatch itself resets it to "contiguous"
+void note_deal(int kid, bool cyclic);
 struct TimedScope {
   hipStream_t s;
   bool on;

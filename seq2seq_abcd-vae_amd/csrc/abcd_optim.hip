@@ -187,6 +187,7 @@ static int timing_sum(int want, double* out) {
 namespace abcd {
 static char g_dispatch[TK_N][128];
 static long g_dispatch_n[TK_N];
+static int g_dispatch_deal[TK_N];
 void note_dispatch(int kid, const char* fmt, ...) {
   if (!tk_valid(kid)) return;
   va_list ap;
@@ -194,6 +195,10 @@ void note_dispatch(int kid, const char* fmt, ...) {
   vsnprintf(g_dispatch[kid], sizeof(g_dispatch[kid]), fmt, ap);
   va_end(ap);
   ++g_dispatch_n[kid];
+  g_dispatch_deal[kid] = 0;
+}
+void note_deal(int kid, bool cyclic) {
+  if (tk_valid(kid)) g_dispatch_deal[kid] = cyclic ? 1 : 0;
 }
 }  // namespace abcd
 
@@ -201,9 +206,13 @@ extern "C" const char* abcd_dispatch_name(int kid) {
   return abcd::tk_valid(kid) ? abcd::g_dispatch[kid] : "";
 }
 extern "C" long abcd_dispatch_count(int kid) { return abcd::tk_valid(kid) ? abcd::g_dispatch_n[kid] : -1; }
+extern "C" int abcd_dispatch_deal(int kid) {
+  return abcd::tk_valid(kid) && abcd::g_dispatch_n[kid] > 0 ? abcd::g_dispatch_deal[kid] : -1;
+}
 extern "C" void abcd_dispatch_reset(void) {
   for (int k = 0; k < abcd::TK_N; ++k) {
     abcd::g_dispatch[k][0] = 0;
+    abcd::g_dispatch_deal[k] = 0;
     abcd::g_dispatch_n[k] = 0;
   }
 }

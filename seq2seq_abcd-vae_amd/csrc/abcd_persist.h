@@ -14,6 +14,27 @@
 
 namespace abcd {
 
+// How a group's 16-row blocks map onto the packed (length-sorted) batch: local
+// block j of row group g is packed block g * gmul + j * jstep, and a packed row
+// is 16 * block + (local row & 15).
+//   contiguous (gmul = blocks per group, jstep = 1): a group is a contiguous
+//     row range, so group 0 holds the longest sequences and keeps every block
+//     of its tile live for nearly the whole launch while the last groups idle;
+//   cyclic (gmul = 1, jstep = groups): block j of group g is block g + ng * j,
+//     so every group owns one long block plus progressively shorter ones and
+//     the critical group sheds blocks as the batch shrinks.
+// Blocks grow with j under both deals, so "block j is past the step's batch"
+// stays monotone in j (the kernels' uniform skip tests).  LDS tiles, partial
+// buffers and sync words stay keyed by (group, local block).
+struct BlockDeal {
+  int gmul, jstep;
+};
+inline BlockDeal block_deal(bool cyclic, int ngroups, int blocks_per_group) {
+  return cyclic ? BlockDeal{1, ngroups} : BlockDeal{blocks_per_group, 1};
+}
+// first packed row of local block j of row group g
+__host__ __device__ inline int deal_row(BlockDeal d, int g, int j) { return 16 * (g * d.gmul + j * d.jstep); }
+
 // One direction of an encoder layer, forward.
 struct PFwdDir {
   const float* Whh;              // G*H x H (torch layout)
@@ -27,6 +48,7 @@ struct PFwdDir {
 struct PFwdArgs {
   PFwdDir d[2];
   int H, nd, T, nrt;
+  BlockDeal deal;    // filled by the launcher
   const int* off;    // device: off[0..T]
   unsigned* sync;    // one 128-B counter line per group, zeroed before the launch
   unsigned long long* prof;  // diagnostics: per-step s_memtime stamps, or null
@@ -45,6 +67,7 @@ struct PBwdArgs {
   PBwdDir d[2];
   int H, nd, T, nrt;
   int B;             // batch (rows of the first step): the 32-row groups of enc_bwd_w8
+  BlockDeal deal;    // filled by the launcher
   const int* off;
   unsigned* sync;
   unsigned long long* prof;
@@ -60,6 +83,7 @@ struct PBwdArgs {
 struct PDecFwdArgs {
   int H, Hm, F, Fp, T, nrt, feedback;
   int flags;                       // hand-off form: 1 per-member flags, 0 group counter
+  BlockDeal deal;                  // filled by the launcher
   const int* off;
   unsigned* sync;
   unsigned long long* prof;
@@ -86,6 +110,7 @@ struct PDecBwdArgs {
   int H, Hm, F, Fp, T, nrt, feedback;
   int B;                           // batch (rows of step 0): the 32-row groups of dec_bwd_w16
   int flags;                       // hand-off form: 1 per-member flags, 0 group counter
+  BlockDeal deal;                  // filled by the launcher
   const int* off;
   unsigned* sync;
   unsigned long long* prof;
@@ -150,6 +175,10 @@ bool dec_bwd_dhid_done();
 
 // ABCD_PERSIST=0 disables the persistent path (parity/timing comparisons).
 bool persist_enabled();
+// ABCD_PERSIST_DEAL (read per call): which roles deal their row blocks
+// cyclically -- a mask of 1 enc fwd, 2 enc bwd, 4 dec fwd, 8 dec bwd; 0 keeps
+// the contiguous deal everywhere; unset: the measured-faster form per kernel.
+bool deal_cyclic(int role_bit);
 
 // Side-stream gate (abcd_side_gate_enable): a deferred decoder backward arms
 // it (side_gate_arm), the first encoder BPTT launched after that on this host

@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256) void enc_fwd_persist(PFwdArgs a) {
   const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform
   const int u0 = mem * 16, unit = u0 + r;
-  const int row0 = rt * PERSIST_ROWS + w * 16;  // this wave's first row inside a step
+  const int row0 = deal_row(a.deal, rt, w);  // this wave's first row inside a step (its block of the deal)
   unsigned* cnt = a.sync + grp * PERSIST_SYNC_STRIDE;
   if (X6) stage_x6(smem, D.Whh, H, H, G, H / 32, 0, H / 32, [&](int j, int rr) { return j * H + u0 + rr; });
   else stage_b_frag(smem, D.Whh, H, G, nch, [&](int j) { return j * H + u0; });
@@ -1110,14 +1110,20 @@ __global__ __launch_bounds__(256) void dec_fwd_x6(PDecFwdArgs a) {
   const int rt = grp;
   const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int row0 = rt * PERSIST_ROWS + w * 16;
+  // first packed row of the group's row block j (the deal; uniform)
+  auto rowb = [&](int j) { return deal_row(a.deal, rt, j); };
+  const int row0 = rowb(w);
   const int u0 = mem * 8, unit = u0 + (r & 7);
   GSync gs{a.sync + grp * PERSIST_SYNC_STRIDE,
            a.sync + ((size_t)2 * a.nrt + PERSIST_REG_LINES + (size_t)grp * PERSIST_FLAG_LINES) * PERSIST_SYNC_STRIDE,
            M, mem, a.flags, 0u};
   // emit roles: tile j2 of [mu | lv] columns, row half `half`; wave part 0 = mu, 1 = lv
   const int j2 = mem >> 1, half = mem & 1, part = w >> 1;
-  const int erow0 = rt * PERSIST_ROWS + 32 * half + 16 * (w & 1);
+  const int erow0 = rowb(2 * half + (w & 1));
+  // the emit product's chunk rotation is keyed by the PACKED 32-row pair of
+  // its rows (the contiguous deal's `half`), not by the member's slot: a row's
+  // accumulation order -- its bits -- then does not depend on the deal
+  const int erot = (2 * j2 + ((erow0 >> 5) & 1)) % NM32;
   const bool has1 = mem < n1t, has2 = j2 < n2t;
   // LDS images
   f4* BC = smem;                        // cell [x | h]: [2][NCC][3][64]
@@ -1145,10 +1151,15 @@ __global__ __launch_bounds__(256) void dec_fwd_x6(PDecFwdArgs a) {
   // ran beside the input projection and delayed it / the encoder's launch
   const int nidle = M - 2 * n2t;
   auto fill_eps = [&](int ts) {
-    const int o1 = a.off[ts], bs1 = a.off[ts + 1] - o1, rows = min(PERSIST_ROWS, bs1 - rt * PERSIST_ROWS);
+    const int o1 = a.off[ts], bs1 = a.off[ts + 1] - o1;
+    // the group's live tile rows of the step: blocks grow with j, so the live
+    // ones are a prefix of the tile and only the last of them can be partial
+    int rows = 0;
+    for (int j = 0; j < PERSIST_ROWS / 16; ++j) rows += max(0, min(16, bs1 - rowb(j)));
     float* ep = const_cast<float*>(a.eps);
     for (int e = (mem - 2 * n2t) * 256 + (int)threadIdx.x; e < rows * F; e += nidle * 256) {
-      const long rr = o1 + rt * PERSIST_ROWS + e / F;
+      const int lr = e / F;
+      const long rr = o1 + rowb(lr >> 4) + (lr & 15);
       const int col = e % F;
       st_sc1(ep + rr * F + col, philox_normal(a.seed, a.offset + (uint64_t)rr * F + col));
     }
@@ -1301,8 +1312,7 @@ __global__ __launch_bounds__(256) void dec_fwd_x6(PDecFwdArgs a) {
       if (erow0 < bs) {
         const BufKC Aa{make_rsrc(a.Aact + (size_t)o * 2 * Hm + part * Hm, (uint32_t)(bs * 2 * Hm - part * Hm) * 4u),
                        (uint32_t)2 * Hm * 4u};
-        wave_mma_x6<1, NM32, 4>(ae, Aa, erow0 + r, B2 + part * NM32 * 3 * 64, NM32, lane, q,
-                                mem % NM32);
+        wave_mma_x6<1, NM32, 4>(ae, Aa, erow0 + r, B2 + part * NM32 * 3 * 64, NM32, lane, q, erot);
       }
 #pragma unroll
       for (int g = 0; g < 4; ++g) ev[g] = col2 < F ? ae[0][g] + b2v : 0.f;
@@ -1605,7 +1615,8 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
   const int ng = a.nrt;  // 32-row groups (the launcher's count)
   const Role role = assign_role(ng, M);
   const int grp = role.grp, mem = role.mem;
-  const int rowg = grp * W16_ROWS;
+  // first packed row of the group's row block rb (the deal; uniform)
+  auto rowb = [&](int rb) { return deal_row(a.deal, grp, rb); };
   const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   GSync gs{a.sync + grp * PERSIST_SYNC_STRIDE,
@@ -1688,11 +1699,17 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
   const bool p0 = pk < 2 * nFt;
   const int prb = !p0 ? 0 : pk < 2 * nfull ? pk / nfull : pk - 2 * nfull;
   const int jx = !p0 ? 0 : pk < 2 * nfull ? pk % nfull : nfull;
-  const int prow0 = rowg + 16 * prb;
+  const int prow0 = rowb(prb);
+  // the producer a unit's dx sum starts at is keyed by the parity of its PACKED
+  // row block (the contiguous deal's prb, i.e. this unit's member there), not
+  // by the member that holds the unit: a row's summation order -- its bits --
+  // then does not depend on the deal
+  const int pbit = (prow0 >> 4) & 1;
+  const int prot = (jx < nfull ? pbit * nfull + jx : 2 * nfull + pbit) % M;
   // P1 dZ unit of this wave: row block w >> 1, column tile 2 mem + (w & 1)
   // P2: dh half-sum of row block w & 1 over producers 8 (w >> 1) .. + 7; waves 0 / 1 run the cell
   const int crb = w & 1;
-  const int crow0 = rowg + 16 * crb;
+  const int crow0 = rowb(crb);
   const bool cellw = w < 2;
   const int unit = u0 + r;
   float carry[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1735,7 +1752,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     if (p0) {
       f4 dx = f4zero();
       if (NXS > 0 && i > 0 && prow0 < succ_valid)  // (lanes of padding columns: out-of-range offsets, no traffic)
-        sum_partials<M>(prd, col0 < F ? xblk(jx, prb) + (uint32_t)lane * 16u : 0x80000000u, dx, mem % M);
+        sum_partials<M>(prd, col0 < F ? xblk(jx, prb) + (uint32_t)lane * 16u : 0x80000000u, dx, prot);
       float dmu[4], dlv[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
@@ -1766,7 +1783,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     // (rows without one have no dG_{t+1}); block k + 1's split runs between
     // block k's 24 MFMAs (as wave_mma_x6p)
     {
-      const int nblk = !dgv ? 0 : rowg + 16 < succ_valid ? 4 : rowg < succ_valid ? 2 : 0;  // uniform
+      const int nblk = !dgv ? 0 : rowb(1) < succ_valid ? 4 : rowb(0) < succ_valid ? 2 : 0;  // uniform
       auto dt_split = [&](int k, bf8 (&v)[3]) {
         const float* ar = DT + (16 * (k >> 1) + r) * W16_DTP + 32 * (k & 1) + 8 * q;
         split8(*reinterpret_cast<const f4*>(ar), *reinterpret_cast<const f4*>(ar + 4), v[0], v[1], v[2]);
@@ -1805,7 +1822,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     float zpre[4];  // the activations of this wave's tile
     {
       const __amdgpu_buffer_rsrc_t rz = make_rsrc(a.Aact + (size_t)o * 2 * Hm, (uint32_t)bs * 2 * Hm * 4u);
-      const int zr0 = rowg + 16 * zrb;
+      const int zr0 = rowb(zrb);
 #pragma unroll
       for (int g = 0; g < 4; ++g)
         zpre[g] = bld(rz, ((uint32_t)(zr0 + 4 * q + g) * 2 * Hm + 32 * mem + 16 * zjj + r) * 4u);
@@ -1814,7 +1831,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     pin(zpre);
     PSTAMP(2);
     {
-      const int zr0 = rowg + 16 * zrb;
+      const int zr0 = rowb(zrb);
       f4 acc[1] = {f4zero()};
       if (zr0 < bs) {
         const __amdgpu_buffer_rsrc_t ra = make_rsrc((ismu ? a.dMU : a.dLV) + (size_t)o * Fp, (uint32_t)bs * Fp * 4u);
@@ -1830,7 +1847,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
 #endif
     __syncthreads();  // the member's 32 x 32 dZ tile is in LDS
     {  // row block 1's split between row block 0's 24 MFMAs
-      const int nrb = rowg + 16 < bs ? 2 : rowg < bs ? 1 : 0;  // uniform
+      const int nrb = rowb(1) < bs ? 2 : rowb(0) < bs ? 1 : 0;  // uniform
       auto zt_split = [&](int rb, bf8 (&v)[3]) {
         const float* ar = ZT + (16 * rb + r) * W16_ZTP + 8 * q;
         split8(*reinterpret_cast<const f4*>(ar), *reinterpret_cast<const f4*>(ar + 4), v[0], v[1], v[2]);
@@ -1874,9 +1891,10 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     // publish's drain does not wait for them
     {
       const int row = threadIdx.x >> 3, qd = 4 * (threadIdx.x & 7);
-      if (rowg + row < bs)
+      const int prow = rowb(row >> 4) + (row & 15);  // the tile row's packed row
+      if (prow < bs)
         st4(make_rsrc(a.dZ + (size_t)o * 2 * Hm, (uint32_t)bs * 2 * Hm * 4u),
-            (uint32_t)((rowg + row) * 2 * Hm + 32 * mem + qd) * 4u,
+            (uint32_t)(prow * 2 * Hm + 32 * mem + qd) * 4u,
             *reinterpret_cast<const f4*>(ZT + row * W16_ZTP + qd), false);
     }
     // ---------------- P2: dh -> cell backward -> dG_t -> dx partials ----------------
@@ -1954,7 +1972,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     if (NXS > 0 && i + 1 < T) {
 #pragma unroll
       for (int rb = 0; rb < 2; ++rb) {
-        if (rowg + 16 * rb >= bs) continue;  // uniform
+        if (rowb(rb) >= bs) continue;  // uniform
         bf8 av[2][3];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -1986,9 +2004,10 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
 #pragma unroll
       for (int k2 = 0; k2 < 2; ++k2) {
         const int k = threadIdx.x + 256 * k2, row = k >> 4, slot = (k >> 2) & 3, qd = 4 * (k & 3);
-        if (rowg + row >= bs) continue;
+        const int prow = rowb(row >> 4) + (row & 15);
+        if (prow >= bs) continue;
         const f4 v = *reinterpret_cast<const f4*>(DT + row * W16_DTP + 16 * slot + qd);
-        const uint32_t so = (uint32_t)((rowg + row) * GH + u0 + qd) * 4u;
+        const uint32_t so = (uint32_t)(prow * GH + u0 + qd) * 4u;
         if constexpr (GRU) {  // dGX = (dr, dz, dn), dGH = (dr, dz, dn r)
           const __amdgpu_buffer_rsrc_t rh = make_rsrc(a.dGH + (size_t)o * GH, (uint32_t)bs * GH * 4u);
           if (slot < 3) st4(rg, so + (uint32_t)(slot * H) * 4u, v, false);
@@ -2009,7 +2028,7 @@ __global__ __launch_bounds__(256) void dec_bwd_w16(PDecBwdArgs a) {
     const __amdgpu_buffer_rsrc_t pw = (T & 1) ? pr1 : pr0;
 #pragma unroll
     for (int rb = 0; rb < 2; ++rb) {
-      if (rowg + 16 * rb >= a.B) continue;  // uniform
+      if (rowb(rb) >= a.B) continue;  // uniform
       f4 h0[4] = {f4zero(), f4zero(), f4zero(), f4zero()};
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
@@ -2092,7 +2111,9 @@ __global__ __launch_bounds__(256) void enc_bwd_w8(PBwdArgs a) {
   const int u0 = mem * 32;
   const int rb = w & 1, uh = w >> 1;        // this wave's cell tile: rows 16 rb .., units u0 + 16 uh ..
   const int unit = u0 + 16 * uh + r;
-  const int rowg = rt * W8_ROWS, row0 = rowg + 16 * rb;
+  // first packed row of the group's row block b2 (the deal; uniform), this wave's cell rows
+  auto rowb = [&](int b2) { return deal_row(a.deal, rt, b2); };
+  const int row0 = rowb(rb);
   unsigned* cnt = a.sync + grp * PERSIST_SYNC_STRIDE;
   // LDS: [wave][subtile j][chunk c - NCR][plane][64] | dG tile [32][132] | wave transposes
   f4* BL = smem;
@@ -2216,7 +2237,7 @@ __global__ __launch_bounds__(256) void enc_bwd_w8(PBwdArgs a) {
       const __amdgpu_buffer_rsrc_t pw = make_rsrc(a.part + (size_t)((i + 1) & 1) * slot_f, (uint32_t)(slot_f * 4));
 #pragma unroll
       for (int b2 = 0; b2 < 2; ++b2) {
-        if (rowg + 16 * b2 >= bs) break;  // uniform: row blocks past the step's batch
+        if (rowb(b2) >= bs) break;  // uniform: row blocks past the step's batch (blocks grow with b2)
         bf8 av[NC][3];
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
@@ -2255,9 +2276,10 @@ __global__ __launch_bounds__(256) void enc_bwd_w8(PBwdArgs a) {
 #pragma unroll
       for (int k2 = 0; k2 < G; ++k2) {
         const int k = threadIdx.x + 256 * k2, row = k / (8 * G), gate = (k >> 3) % G, qd = 4 * (k & 7);
-        if (rowg + row >= bs) continue;
+        const int prow = rowb(row >> 4) + (row & 15);  // the tile row's packed row
+        if (prow >= bs) continue;
         const f4 v = *reinterpret_cast<const f4*>(DT + row * W8_DTP + 32 * gate + qd);
-        const uint32_t so = (uint32_t)((rowg + row) * GH + gate * H + u0 + qd) * 4u;
+        const uint32_t so = (uint32_t)(prow * GH + gate * H + u0 + qd) * 4u;
         if (G == 3) {
           st4(rh, so, v, false);
           if (gate < 2) st4(rx, so, v, false);
@@ -2281,6 +2303,15 @@ __global__ __launch_bounds__(256) void enc_bwd_w8(PBwdArgs a) {
 bool persist_enabled() {
   const char* v = getenv("ABCD_PERSIST");  // read per call: tests flip it in-process
   return !(v && v[0] == '0');
+}
+
+// The deal of the 16-row blocks (abcd_persist.h: BlockDeal) of the four forms
+// the H = 256 configurations dispatch.  Same-box A/B per role: DESIGN.md s5.
+constexpr int DEAL_DEFAULT = 15;  // 1 enc fwd, 2 enc bwd, 4 dec fwd, 8 dec bwd
+bool deal_cyclic(int role_bit) {
+  const char* v = getenv("ABCD_PERSIST_DEAL");  // read per call: tests flip it in-process
+  const int mask = v && v[0] ? atoi(v) : DEAL_DEFAULT;
+  return (mask & role_bit) != 0;
 }
 
 // Pinned ring of offset tables.  upload_offsets copies one to the device with
@@ -2564,12 +2595,15 @@ static int launch_fwd(hipStream_t s, const PFwdArgs& a, bool* launched) {
   if (!ok) return 0;
   ABCD_TRY(zero_sync(s, a.sync, a.nd * a.nrt));
   PFwdArgs b = a;
+  const bool cyc = deal_cyclic(1);
+  b.deal = block_deal(cyc, a.nrt, PERSIST_ROWS / 16);
   b.prof = (g_prof_mask & 1) ? g_prof : nullptr;
   {
     TimedScope ts(s, TK_ENC_FWD);
     enc_fwd_persist<G, PD, X6><<<grid, 256, lds, s>>>(b);
   }
   note_dispatch(TK_ENC_FWD, "enc_fwd_persist<%d,%d,%d> grid %d", G, PD, X6, grid);
+  note_deal(TK_ENC_FWD, cyc);
   ABCD_CHECK_LAUNCH();
   *launched = true;
   return 0;
@@ -2656,6 +2690,8 @@ static int launch_bwd_w8(hipStream_t s, const PBwdArgs& a, bool* launched) {
   ABCD_TRY(zero_sync(s, a.sync, a.nd * nrt));
   PBwdArgs b = a;
   b.nrt = nrt;
+  const bool cyc = deal_cyclic(2);
+  b.deal = block_deal(cyc, nrt, W8_ROWS / 16);
   b.prof = (g_prof_mask & 2) ? g_prof : nullptr;
   {
     TimedScope ts(s, TK_ENC_BWD);
@@ -2663,6 +2699,7 @@ static int launch_bwd_w8(hipStream_t s, const PBwdArgs& a, bool* launched) {
     enc_bwd_w8<G><<<grid, 256, lds, s>>>(b);
   }
   note_dispatch(TK_ENC_BWD, "enc_bwd_w8<%d> grid %d", G, grid);
+  note_deal(TK_ENC_BWD, cyc);
   ABCD_CHECK_LAUNCH();
   *launched = true;
   return 0;
@@ -2738,12 +2775,15 @@ static int launch_dec_fwd_x6_k(hipStream_t s, const PDecFwdArgs& a, bool* launch
   PDecFwdArgs b = a;
   if (!inkernel) b.eps_fill = 0;
   b.flags = 1;  // per-member flags (the group-counter form measured slower)
+  const bool cyc = deal_cyclic(4);
+  b.deal = block_deal(cyc, a.nrt, PERSIST_ROWS / 16);
   b.prof = (g_prof_mask & 4) ? g_prof : nullptr;
   {
     TimedScope ts(s, TK_DEC_FWD);
     dec_fwd_x6<NCC, NH32, NM32, GRU, HPRE><<<grid, 256, lds, s>>>(b);
   }
   note_dispatch(TK_DEC_FWD, "dec_fwd_x6<%d,%d,%d,%s> grid %d", NCC, NH32, NM32, GRU ? "GRU" : "LSTM", grid);
+  note_deal(TK_DEC_FWD, cyc);
   ABCD_CHECK_LAUNCH();
   *launched = true;
   return 0;
@@ -2805,12 +2845,15 @@ static int launch_dec_bwd_w16(hipStream_t s, const PDecBwdArgs& a, bool* launche
   PDecBwdArgs b = a;
   b.nrt = ng;
   b.flags = 1;
+  const bool cyc = deal_cyclic(8);
+  b.deal = block_deal(cyc, ng, W16_ROWS / 16);
   b.prof = (g_prof_mask & 8) ? g_prof : nullptr;
   {
     TimedScope ts(s, TK_DEC_BWD);
     dec_bwd_w16<NXS, GRU><<<grid, 256, lds, s>>>(b);
   }
   note_dispatch(TK_DEC_BWD, "dec_bwd_w16<%d,%s> grid %d", NXS, GRU ? "GRU" : "LSTM", grid);
+  note_deal(TK_DEC_BWD, cyc);
   tl_dec_bwd_dhid = b.dhid != nullptr;
   ABCD_CHECK_LAUNCH();
   *launched = true;

@@ -242,6 +242,7 @@ _SIGS = {
     "abcd_dispatch_name": (ctypes.c_char_p, [c_int]),
     "abcd_dispatch_count": (c_long, [c_int]),
     "abcd_dispatch_reset": (None, []),
+    "abcd_dispatch_deal": (c_int, [c_int]),
     "abcd_debug_persist_prof": (None, [c_void_p, c_int]),
     "abcd_debug_gemm_route": (ctypes.c_char_p, []),
     "abcd_debug_gemm_side": (None, [c_int]),
@@ -441,6 +442,13 @@ def dispatch():
                                 ("seg_losses", SEG_LOSSES), ("kl_rows", KL_ROWS),
                                 ("pair_nll", PAIR_NLL), ("pair_post", PAIR_POST),
                                 ("griffin_lim", GRIFFIN_LIM))}
+
+
+def dispatch_deal():
+    """{role: 1 cyclic / 0 contiguous block deal of the role's last launch, -1: none}"""
+    L = lib()
+    return {r: int(L.abcd_dispatch_deal(k))
+            for r, k in (("enc_fwd", ENC_FWD), ("enc_bwd", ENC_BWD), ("dec_fwd", DEC_FWD), ("dec_bwd", DEC_BWD))}
 
 
 def ptr_array(tensors):
