@@ -1063,6 +1063,121 @@ int abcd_warp_segment_window(const float* cost, long ld_cost, long n0, long n1, 
                              size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------
+ * Posteriors under the time-warped cut: the sum half of
+ * abcd_warp_segment_window.  cost, proto_offset_logits (v),
+ * log_move (HOST, three doubles), log_enter, gap, seg_bonus, log_trans,
+ * log_init and s_min are those of abcd_warp_segment_window; scale is 1 /
+ * temperature and multiplies every term (e, cont, last, log_move, log_enter,
+ * gap, seg_bonus, log_trans, log_init) in fp64 after widening, so scale = 1 is
+ * exact.  cont[k,s] = sp(v[s,k]) and last[k,s] = sp(-v[s,k]) are formed before
+ * the multiplication.  Below every symbol is the multiplied term (lm, le, lt,
+ * li, bonus), T = T_proto; a candidate that is NaN or -inf is excluded, a NaN
+ * or +inf e excludes its cell in both sweeps; LAE is logaddexp, LSE the
+ * log-sum-exp over the admissible candidates, -inf over none:
+ *   G[0] = 0,  G[n] = G[n-1] + gap[n-1]                    (gap NULL: -inf for n >= 1)
+ *   aW[0][k] = -inf,  aH[-1][k][s] = -inf
+ *   n = 0 .. N-1:
+ *     aU[n][k]    = LAE(G[n] + li[k], LSE_k' (aW[n][k'] + lt[k'][k]))
+ *     aA[n][k][0] = LAE(aU[n][k] + le[k], aH[n-1][k][0] + lm[0])
+ *     aA[n][k][s] = LSE_{m in 0..2, s-m >= 0} (aH[n-1][k][s-m] + lm[m])                 s >= 1
+ *     aB[n][k][s] = aA[n][k][s] - e(n,k,s)
+ *     aH[n][k][s] = aB[n][k][s] - cont[k,s]
+ *     aX[n+1][k]  = LSE_{s >= s_min} (aB[n][k][s] - last[k,s]) + bonus
+ *     aW[n+1][k]  = LAE(aW[n][k] + gap[n], aX[n+1][k])
+ *   aU[N][k] = -inf,  aX[0][k] = -inf
+ *   log_z = LAE(G[N], LSE_k aW[N][k])
+ *   bW[N][k] = 0,  bG[N] = 0,  bU[N][k] = -inf;   n = N-1 .. 0:
+ *     bA[n][k][s] = -e(n,k,s) + LAE( [s >= s_min] (-last[k,s] + bonus + bW[n+1][k]),
+ *                                    [n < N-1]    (-cont[k,s] + LSE_{m, s+m < T} (lm[m] + bA[n+1][k][s+m])) )
+ *     bU[n][k] = le[k] + bA[n][k][0]
+ *     bW[n][k] = LAE(gap[n] + bW[n+1][k], LSE_k'' (lt[k][k''] + bU[n][k'']))
+ *     bG[n]    = LAE(gap[n] + bG[n+1], LSE_k (li[k] + bU[n][k]))                        (bG[0] = log_z)
+ *   post_k[n K + k]             = exp(aU[n][k] + bU[n][k] - log_z)     a segment of k starts at frame n
+ *   post_k[(N + 1) K + n K + k] = exp(aX[n][k] + bW[n][k] - log_z)     a segment of k ends before frame n
+ *   gap_post[n]   = exp(LAE(G[n] + bG[n+1], LSE_k (aW[n][k] + bW[n+1][k])) + gap[n] - log_z),  n < N;  [N] = 0
+ *   init_counts[k]         = sum_{n < N} exp(G[n] + li[k] + bU[n][k] - log_z)
+ *   trans_counts[k' K + k] = sum_{n < N} exp(aW[n][k'] + lt[k'][k] + bU[n][k] - log_z)
+ *   move_counts[3 k + m]   = sum_{n <= N-2} sum_{s, s+m < T} exp(aH[n][k][s] + lm[m] + bA[n+1][k][s+m] - log_z)
+ * log_z = -inf (no cover) makes every posterior and count 0.  +inf anywhere
+ * but in e is outside the contract.
+ *
+ * The programme lives in the workspace, which must not be touched between the
+ * calls of a recording; doubles in this order, cells = (N + 1) K and S = K T:
+ * G and bG (N + 1 each), the lattice aU, aX, aW, bU, bW (cells each), cont and
+ * last (S each, row s K + k, formed by the forward call with n0 = 0), the two
+ * alternating rows of aH (forward) or bA (backward) (2 S; frame n is row n mod
+ * 2), the count accumulators (K K bigram, K initial, 3 K move), log_z, and
+ * three 64-bit integers: the next frame of the forward sweep, the next n1 of
+ * the backward sweep, the status of the last backward call.
+ *
+ * abcd_warp_posterior_forward: frames n0 .. n1 - 1 ascending on the plane whose
+ * row 0 is frame n0; calls go in order on ONE stream with the same arguments
+ * but cost, alpha_out, n0 and n1; n0 = 0 starts over.  A call whose n0 is not
+ * the carried frame runs nothing, writes log_z = NaN and leaves the carry as it
+ * is.  The call with n1 = N writes log_z; no other call writes it.  alpha_out
+ * (may be NULL) receives aH[n][k][s] at alpha_out[(n - n0) ld_alpha + s K + k].
+ *
+ * abcd_warp_posterior_backward: frames n1 - 1 .. n0 descending after the
+ * forward sweep has finished, the first call with n1 = N, every next call's n1
+ * the previous n0, each on the plane of ITS frames (row 0 = frame n0) and, for
+ * move_counts, on the rows alpha_out received for them (row 0 = frame n0).
+ * A call out of order (or before the forward sweep is through) runs nothing,
+ * changes no lattice entry, count or carried frame and sets the status word to
+ * 1; a call in order sets it to 0.  The call with n0 = 0 forms bG, writes
+ * post_k (2 (N + 1) K), gap_post (N + 1) and the counts that were asked for:
+ * trans_counts (K x K, row stride K) and init_counts (K) together or not at
+ * all, move_counts (3 K) only with alpha.  n1 = N starts the sweep over.
+ *
+ * One workgroup of 1024 threads, abcd_warp_segment_window's grid: with R =
+ * 1024 / K thread r K + k owns the states s = r, r + R, ... of category k and
+ * the k' = r, r + R, ... of column k.  log_trans is resident in LDS up to K =
+ * 128 (K rows of K + 1 floats) and streamed above (abcd_warp_posterior_plan
+ * says which, with the launch width and the LDS bytes; it is a pure
+ * function).  Every thread keeps a (maximum, sum of exp(c - maximum)) pair per
+ * reduction; the pairs of aU, aX and bW's chain term meet in LDS and thread k
+ * joins them in r order.  A count entry is owned by one thread and summed in
+ * the order the backward sweep visits the frames (a move count: the threads'
+ * parts of a frame joined in r order by thread k).  No atomics, no
+ * device-global word, nothing is allocated.  Any split of 0 .. N into forward
+ * calls and any split into backward calls gives the one-call bits, two runs
+ * agree bit for bit, and passing or omitting alpha_out, alpha or the count
+ * buffers changes no other output's bits.
+ * Limits: those of abcd_warp_segment_window; the workspace query returns 0
+ * beyond them.  ABCD_EINVAL (on the host before any launch, nothing is
+ * written): those limits and argument rules, scale not finite or not positive,
+ * ld_alpha < K T_proto with a plane given, move_counts without alpha, exactly
+ * one of the two bigram buffers, a NULL log_z (forward) or post_k / gap_post
+ * (backward), a missing or short workspace.  N = 0 (n0 = n1 = 0): the forward
+ * call writes log_z = 0, the backward call zero posteriors and counts; neither
+ * reads anything nor touches the workspace.
+ *
+ * Measured on one MI355X at N = 15 000, K = 128, T_proto = 200, F = 129
+ * (profiles/warppost_bench.json), the plane read from HBM in
+ * 6 chunks: the forward sweep 1218.5 ms (81.2 us per frame; 1228.6 keeping
+ * aH), the backward sweep 1518.3 ms without counts (101.2 us per frame),
+ * 1626.4 with the bigram counts, 1944.4 with the move counts, 2052.6 with
+ * both; segment_warp_posteriors end to end 2668.4 ms (3284.7 with every
+ * count), against abcd_warp_segment_window on the same plane in the same
+ * process, 785.5 ms: derived, the two sweeps take 3.48 x the best-path
+ * programme.  State 78.0 MB; the aH plane of the move counts 3.07 GB.
+ *
+ * No timing or dispatch id is assigned to these entry points.
+ * ---------------------------------------------------------------------- */
+int abcd_warp_posterior_plan(int K, int T_proto, int* resident, int* threads, size_t* lds_bytes);
+size_t abcd_warp_posterior_workspace_bytes(long N, int K, int T_proto);
+int abcd_warp_posterior_forward(const float* cost, long ld_cost, long n0, long n1, long N, int K, int T_proto,
+                                const float* proto_offset_logits, const double* log_move, const float* log_enter,
+                                const float* gap, double seg_bonus, double scale, const float* log_trans,
+                                long ld_trans, const float* log_init, int s_min, double* alpha_out, long ld_alpha,
+                                double* log_z, void* ws, size_t ws_bytes, void* stream);
+int abcd_warp_posterior_backward(const float* cost, long ld_cost, long n0, long n1, long N, int K, int T_proto,
+                                 const float* proto_offset_logits, const double* log_move, const float* log_enter,
+                                 const float* gap, double seg_bonus, double scale, const float* log_trans,
+                                 long ld_trans, const float* log_init, int s_min, const double* alpha, long ld_alpha,
+                                 double* post_k, double* gap_post, double* trans_counts, double* init_counts,
+                                 double* move_counts, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * Featurisation + packing on the device: replaces the per-item host path
  * Dataset.__getitem__ -> STFT.__call__ -> log_and_normalize -> pack_sequence
  * (data_utils.py:88-103, 124-139, 165-182; learning.py:466-470) for a whole

@@ -207,6 +207,16 @@ _SIGS = {
     "abcd_warp_segment_window": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_void_p,
                                          _P(c_double), c_void_p, c_void_p, c_double, c_void_p, c_long, c_void_p,
                                          c_int] + [c_void_p] * 11 + [c_size_t, c_void_p]),
+    "abcd_warp_posterior_plan": (c_int, [c_int, c_int, _P(c_int), _P(c_int), _P(c_size_t)]),
+    "abcd_warp_posterior_workspace_bytes": (c_size_t, [c_long, c_int, c_int]),
+    "abcd_warp_posterior_forward": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_void_p,
+                                            _P(c_double), c_void_p, c_void_p, c_double, c_double, c_void_p, c_long,
+                                            c_void_p, c_int, c_void_p, c_long, c_void_p, c_void_p, c_size_t,
+                                            c_void_p]),
+    "abcd_warp_posterior_backward": (c_int, [c_void_p, c_long, c_long, c_long, c_long, c_int, c_int, c_void_p,
+                                             _P(c_double), c_void_p, c_void_p, c_double, c_double, c_void_p, c_long,
+                                             c_void_p, c_int, c_void_p, c_long] + [c_void_p] * 6 +
+                                     [c_size_t, c_void_p]),
     "abcd_stft_frames": (c_int, [ctypes.c_longlong, c_int, c_int, c_int]),
     "abcd_featurize_workspace_bytes": (c_size_t, [c_int, c_int]),
     "abcd_featurize_packed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float,
@@ -306,7 +316,7 @@ def source_hash():
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "csrc")
     names = ["abcd_gemm.hip", "abcd_rnn.hip", "abcd_persist.hip", "abcd_sampler.hip", "abcd_optim.hip",
              "abcd_feat.hip", "abcd_generate.hip", "abcd_score.hip", "abcd_pairwise.hip", "abcd_vocoder.hip", "abcd_chain.hip", "abcd_span.hip",
-             "abcd_warp.hip", "abcd_warpseg.hip", "abcd_common.h", "abcd_emtile.h", "abcd_internal.h",
+             "abcd_warp.hip", "abcd_warpseg.hip", "abcd_warppost.hip", "abcd_common.h", "abcd_emtile.h", "abcd_internal.h",
              "abcd_persist.h", "abcd_special.h", "abcd_x6.h", "../../include/abcd_hip.h"]
     h = hashlib.sha256()
     for n in sorted(names):

@@ -39,13 +39,15 @@ operator                   replaces (reference)                            C ent
 ``abcd::span_chain_viterbi_window`` (none: that cover, the table in windows) ``abcd_span_chain_viterbi_window``
 ``abcd::frame_costs``      (none: frames against every prototype step)     ``abcd_frame_costs``
 ``abcd::warp_segment_window`` (none: the cut with warped prototypes)       ``abcd_warp_segment_window``
+``abcd::warp_posterior_forward`` (none: the sum half of that cut, forward) ``abcd_warp_posterior_forward``
+``abcd::warp_posterior_backward`` (none: its backward sweep and counts)    ``abcd_warp_posterior_backward``
 =========================  ==============================================  =========================================
 
-The last eighteen are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
+The last twenty are forward-only (scoring, synthesis, segmentation, alignment): they have no autograd
 formula and raise when an input requires grad outside ``torch.no_grad()``.
 
-``span_chain_viterbi_window`` and ``warp_segment_window`` are the operators that are NOT functional: they
-carry a recording's programme from call to call in a state tensor they mutate
+``span_chain_viterbi_window``, ``warp_segment_window`` and the two ``warp_posterior`` sweeps are the
+operators that are NOT functional: they carry a recording's programme from call to call in a state tensor they mutate
 (``STATEFUL_OPS``; ``OPS`` lists the functional ones).
 
 Operators take tensors, ints and floats only (no module objects): the
@@ -1538,6 +1540,178 @@ def _(cost, n0, n1, n, K, proto_offset_logits, log_moves, log_enter, gap, seg_bo
 
 
 # ----------------------------------------------------------------------------
+# posteriors under the time-warped cut (forward-only, stateful)
+# ----------------------------------------------------------------------------
+def _warp_posterior_words(n, K, T):
+    """How many doubles of the state precede log_z (abcd_warp_posterior_workspace_bytes' layout)."""
+    return 2 * (n + 1) + 5 * (n + 1) * K + 4 * K * T + K * K + 4 * K
+
+
+def warp_posterior_state(n, K, T, device=None):
+    """The state tensor ``warp_posterior_forward`` / ``warp_posterior_backward``
+    carry a recording of ``n`` frames in (uint8;
+    abcd_warp_posterior_workspace_bytes: 8 (2 (n + 1) + 5 (n + 1) K + 4 K T + K K
+    + 4 K + 4) bytes and a little).  Doubles in this order: G, bG (n + 1 each),
+    aU, aX, aW, bU, bW ((n + 1) K each), sp(v), sp(-v) (K T each), the two
+    alternating aH / bA rows (2 K T), the count accumulators (K K, K, 3 K),
+    log_z, then the next forward frame, the next backward n1 and the status of
+    the last backward call (64-bit integers, zero in a new state)."""
+    n, K, T = int(n), int(K), int(T)
+    nbytes = N.lib().abcd_warp_posterior_workspace_bytes(n, K, T)
+    if nbytes == 0:
+        raise N.HipError(f"warp_posterior: unsupported shape ({_WARPSEG_LIMIT}); N = {n}, K = {K}, T_proto = {T}")
+    state = N.workspace(nbytes, device if device is not None else torch.device("cuda"))
+    state[8 * _warp_posterior_words(n, K, T):].zero_()
+    return state
+
+
+def warp_posterior_planes(state, n, K, T):
+    """Views into a ``warp_posterior_state``: dict of ``cont``, ``last`` (T x K),
+    ``lattice`` (5 x (n + 1) x K: aU, aX, aW, bU, bW), ``G``, ``bG`` (n + 1),
+    ``log_z`` (0-d) (float64) and ``next`` (3 int64: the next forward frame, the
+    next backward n1, the last backward call's status)."""
+    n, K, T = int(n), int(K), int(T)
+    words = _warp_posterior_words(n, K, T)
+    d = state[:8 * (words + 1)].view(torch.float64)
+    cells, S = (n + 1) * K, K * T
+    at = 2 * (n + 1)
+    lattice = d[at:at + 5 * cells].view(5, n + 1, K)
+    at += 5 * cells
+    return dict(G=d[:n + 1], bG=d[n + 1:2 * (n + 1)], lattice=lattice, cont=d[at:at + S].view(T, K),
+                last=d[at + S:at + 2 * S].view(T, K), log_z=d[words],
+                next=state[8 * (words + 1):8 * (words + 4)].view(torch.int64))
+
+
+def _warp_posterior_args(name, cost, n0, n1, n, K, proto_offset_logits, log_moves, log_enter, gap, scale, log_trans,
+                         log_init, s_min, state, alpha):
+    """The checks the two sweeps share (the plain ones first: they need no device) -> the C calls' inputs."""
+    n0, n1, n, K, s_min, scale = int(n0), int(n1), int(n), int(K), int(s_min), float(scale)
+    moves = _log_moves_arg(name, log_moves)
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"{name}: scale must be positive and finite, got {scale}")
+    S = int(proto_offset_logits.numel())
+    if K < 1 or S < K or S % K:
+        raise ValueError(f"{name}: proto_offset_logits must hold T_proto * {K} entries, got {S}")
+    T = S // K
+    if K > 1024:
+        raise ValueError(f"{name}: at most 1024 categories, got {K}")
+    if not (0 <= n0 < n1 <= n or n0 == n1 == n == 0):
+        raise ValueError(f"{name}: 0 <= n0 < n1 <= N, got {n0}, {n1} and N = {n}")
+    if cost.dim() != 2 or cost.shape[0] < n1 - n0 or cost.shape[1] != S:
+        raise ValueError(f"{name}: cost must hold at least {n1 - n0} rows of {S}, got {tuple(cost.shape)}")
+    if not 0 <= s_min < T:
+        raise ValueError(f"{name}: s_min must lie in 0 .. {T - 1}, got {s_min}")
+    if tuple(log_trans.shape) != (K, K) or log_init.numel() != K:
+        raise ValueError(f"{name}: log_trans must be {K} x {K} and log_init hold {K} entries, got "
+                         f"{tuple(log_trans.shape)} and {tuple(log_init.shape)}")
+    if log_enter is not None and log_enter.numel() != K:
+        raise ValueError(f"{name}: log_enter must hold {K} entries, got {log_enter.numel()}")
+    if gap is not None and gap.numel() != n:
+        raise ValueError(f"{name}: gap must hold {n} entries, got {gap.numel()}")
+    if alpha is not None and (alpha.dim() != 2 or alpha.shape[0] < n1 - n0 or alpha.shape[1] != S or
+                              alpha.dtype != torch.float64 or not alpha.is_contiguous()):
+        raise ValueError(f"{name}: alpha must hold at least {n1 - n0} rows of {S} contiguous float64, got "
+                         f"{tuple(alpha.shape)} {alpha.dtype}")
+    if state.dtype != torch.uint8 or state.dim() != 1 or not state.is_contiguous():
+        raise ValueError(f"{name}: state must be warp_posterior_state({n}, {K}, {T})")
+    for t in (cost, proto_offset_logits, log_trans, log_init, state, log_enter, alpha):
+        if t is not None:
+            N.require_gpu(t)
+    nbytes = N.lib().abcd_warp_posterior_workspace_bytes(n, K, T)
+    if nbytes == 0 or state.numel() < nbytes:
+        raise ValueError(f"{name}: state must be warp_posterior_state({n}, {K}, {T})")
+    ol = proto_offset_logits.float().contiguous()
+    le = None if log_enter is None else log_enter.float().contiguous()
+    c, ldc = _rows(cost.float())
+    lt, ldt = _rows(log_trans.float())
+    li = log_init.float().contiguous()
+    g = _gap_arg(name, gap, n)
+    keep = (ol, le, c, lt, li, g)
+    return (N.ptr(c), ldc, n0, n1, n, K, T, N.ptr(ol), moves, N.ptr(le), N.ptr(g)), (N.ptr(lt), ldt, N.ptr(li),
+                                                                                    s_min), T, S, keep
+
+
+@torch.library.custom_op("abcd::warp_posterior_forward", mutates_args=("state", "alpha"))
+def warp_posterior_forward(cost: Tensor, n0: int, n1: int, n: int, K: int, proto_offset_logits: Tensor,
+                           log_moves: List[float], log_enter: Optional[Tensor], gap: Optional[Tensor],
+                           seg_bonus: float, scale: float, log_trans: Tensor, log_init: Tensor, s_min: int,
+                           state: Tensor, alpha: Optional[Tensor]) -> Tensor:
+    """Frames n0 .. n1 - 1 of the forward sweep of the posteriors under the
+    time-warped cut, on frame_costs' plane of those frames (row 0 is frame n0),
+    the programme being carried in ``state`` (warp_posterior_state; mutated)
+    and, when given, the aH rows of these frames written to ``alpha`` (at least
+    n1 - n0 rows of T_proto K fp64; row 0 is frame n0; mutated)
+    (abcd_warp_posterior_forward).  Calls run in order on one stream: n0 = 0
+    first, then every n0 the previous n1.  -> log_z (0-d fp64): the log evidence
+    from the call with n1 = n, NaN before that and after a call out of order.
+    ``scale`` (1 / temperature) multiplies every term in fp64."""
+    a, b, T, S, keep = _warp_posterior_args("warp_posterior_forward", cost, n0, n1, n, K, proto_offset_logits,
+                                            log_moves, log_enter, gap, scale, log_trans, log_init, s_min, state, alpha)
+    log_z = torch.full((), float("nan"), dtype=torch.float64, device=cost.device)
+    N.check(N.lib().abcd_warp_posterior_forward(*a, float(seg_bonus), float(scale), *b, N.ptr(alpha), S, N.ptr(log_z),
+                                                N.ptr(state), state.numel(), N.stream()), "warp posterior forward")
+    return log_z
+
+
+@warp_posterior_forward.register_fake
+def _(cost, n0, n1, n, K, proto_offset_logits, log_moves, log_enter, gap, seg_bonus, scale, log_trans, log_init,
+      s_min, state, alpha):
+    return cost.new_empty((), dtype=torch.float64)
+
+
+@torch.library.custom_op("abcd::warp_posterior_backward", mutates_args=("state",))
+def warp_posterior_backward(cost: Tensor, n0: int, n1: int, n: int, K: int, proto_offset_logits: Tensor,
+                            log_moves: List[float], log_enter: Optional[Tensor], gap: Optional[Tensor],
+                            seg_bonus: float, scale: float, log_trans: Tensor, log_init: Tensor, s_min: int,
+                            state: Tensor, alpha: Optional[Tensor], want_counts: bool,
+                            want_moves: bool) -> List[Tensor]:
+    """Frames n1 - 1 .. n0 of the backward sweep, after the forward sweep has
+    finished: the first call has n1 = n, every next call's n1 is the previous
+    n0; ``cost`` is the plane of THESE frames (row 0 is frame n0) and ``alpha``
+    (needed by ``want_moves``) the rows ``warp_posterior_forward`` wrote for
+    them (abcd_warp_posterior_backward).  A call out of order raises
+    RuntimeError and leaves the carried programme usable.  -> [post_k (2 x (n +
+    1) x K: onset, end), gap_post (n + 1), trans_counts (K x K), init_counts (K),
+    move_counts (K x 3: stay, step, skip)], fp64, written by the call with n0 =
+    0 (NaN before that); the counts are empty tensors unless asked for."""
+    want_counts, want_moves = bool(want_counts), bool(want_moves)
+    if want_moves and alpha is None:
+        raise ValueError("warp_posterior_backward: want_moves needs alpha, the aH rows of the forward sweep")
+    a, b, T, S, keep = _warp_posterior_args("warp_posterior_backward", cost, n0, n1, n, K, proto_offset_logits,
+                                            log_moves, log_enter, gap, scale, log_trans, log_init, s_min, state, alpha)
+    n0, n, K = int(n0), int(n), int(K)
+    f64 = dict(dtype=torch.float64, device=cost.device)
+    fill = 0.0 if n0 == 0 else float("nan")
+    post_k, gap_post = torch.full((2, n + 1, K), fill, **f64), torch.full((n + 1,), fill, **f64)
+    tc = torch.full((K, K) if want_counts else (0, 0), fill, **f64)
+    ic = torch.full((K if want_counts else 0,), fill, **f64)
+    mc = torch.full((K, 3) if want_moves else (0, 3), fill, **f64)
+    N.check(N.lib().abcd_warp_posterior_backward(*a, float(seg_bonus), float(scale), *b, N.ptr(alpha), S,
+                                                 N.ptr(post_k), N.ptr(gap_post), N.ptr(tc) if want_counts else None,
+                                                 N.ptr(ic) if want_counts else None,
+                                                 N.ptr(mc) if want_moves else None, N.ptr(state), state.numel(),
+                                                 N.stream()), "warp posterior backward")
+    if n > 0:
+        words = _warp_posterior_words(n, K, T)
+        if int(state[8 * (words + 3):8 * (words + 4)].view(torch.int64).item()) != 0:
+            raise RuntimeError(f"warp_posterior_backward: the call for frames {n0} .. {int(n1) - 1} is out of order "
+                               "(the forward sweep is not through, or n1 is not the frame the sweep has reached); "
+                               "nothing was run")
+    return [post_k, gap_post, tc, ic, mc]
+
+
+@warp_posterior_backward.register_fake
+def _(cost, n0, n1, n, K, proto_offset_logits, log_moves, log_enter, gap, seg_bonus, scale, log_trans, log_init,
+      s_min, state, alpha, want_counts, want_moves):
+    n, K = int(n), int(K)
+
+    def e(*shape):
+        return cost.new_empty(shape, dtype=torch.float64)
+    return [e(2, n + 1, K), e(n + 1), e(K, K) if want_counts else e(0, 0), e(K) if want_counts else e(0),
+            e(K, 3) if want_moves else e(0, 3)]
+
+
+# ----------------------------------------------------------------------------
 # log-spectra back to audio (forward-only)
 # ----------------------------------------------------------------------------
 @torch.library.custom_op("abcd::griffin_lim", mutates_args=())
@@ -1594,7 +1768,8 @@ OPS = ("encoder", "encoder_bwd", "sampler", "sampler_bwd", "sampler_sample", "sa
        "pairwise_nll", "pair_posterior", "griffin_lim", "chain_posterior", "span_scores", "span_viterbi",
        "warp_nll", "warp_path", "span_evidence", "span_posterior", "span_table", "span_chain_viterbi",
        "span_chain_posterior", "frame_costs")
-STATEFUL_OPS = ("span_chain_viterbi_window", "warp_segment_window")  # mutate a state argument: kept apart from the functional OPS
+STATEFUL_OPS = ("span_chain_viterbi_window", "warp_segment_window", "warp_posterior_forward",
+                "warp_posterior_backward")  # mutate a state argument: kept apart from the functional OPS
 
 
 def registered() -> Sequence[str]:

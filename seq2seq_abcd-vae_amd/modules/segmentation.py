@@ -23,7 +23,9 @@ each window's table is built from a slice of the frames and
 ``segment_chain_posteriors`` is the sum half of that programme (onset, end,
 gap, span and label posteriors, the evidence and the expected bigram counts
 under the chain, ``ops.span_chain_posterior``) and ``refit_transitions_em``
-fits the chain by EM on those counts."""
+fits the chain by EM on those counts.  ``segment_frames_warped`` cuts with the
+prototypes time-warped inside the programme; ``segment_warp_posteriors`` is its
+sum half and ``refit_warp_em`` fits the moves and the chain under it by EM."""
 import bisect
 import math
 
@@ -257,6 +259,38 @@ def default_chunk_frames(steps, K, budget=PLANE_BUDGET_BYTES):
     return max(1, int(budget) // (4 * int(steps) * int(K)))
 
 
+def _warped_plain_args(name, prototypes, steps, min_state, chunk_frames, log_moves, log_weight):
+    """The plain arguments of the warped entry points, whose errors need no device -> (T, s_min, K, chunk, lm)."""
+    offl = prototypes[2]
+    T, s_min = int(steps), int(min_state)
+    if offl.dim() != 2 or not 1 <= T <= int(offl.shape[0]):
+        raise ValueError(f"{name}: 1 <= steps <= the prototypes' {int(offl.shape[0])} steps, got {T}")
+    if not 0 <= s_min < T:
+        raise ValueError(f"{name}: min_state must lie in 0 .. {T - 1}, got {s_min}")
+    K = int(offl.shape[1])
+    chunk = default_chunk_frames(T, K) if chunk_frames is None else int(chunk_frames)
+    if chunk < 1:
+        raise ValueError(f"{name}: chunk_frames must be at least 1, got {chunk_frames}")
+    lm = list(ops._log_moves_arg(name, log_moves))
+    if log_weight is not None and torch.as_tensor(log_weight).numel() != K:
+        raise ValueError(f"{name}: log_weight must hold {K} entries, got {torch.as_tensor(log_weight).numel()}")
+    return T, s_min, K, chunk, lm
+
+
+def _warped_device_args(name, prototypes, frames, transitions, log_weight, include_weight, K):
+    """-> (n, device, log_trans, log_init, log_enter) of the warped entry points, on the frames' device."""
+    N.require_gpu(frames)
+    n = int(frames.shape[0])
+    dev = frames.device
+    lw = None if log_weight is None else torch.as_tensor(log_weight, device=dev).float().reshape(-1)
+    if transitions is None:
+        lt, li, le = torch.zeros(K, K, device=dev), torch.zeros(K, device=dev), lw
+    else:
+        lt, li, _ = _chain_setup(name, transitions, prototypes, dev)
+        le = lw if include_weight else None
+    return n, dev, lt, li, le
+
+
 def segment_frames_warped(decoder, prototypes, frames, steps, log_moves=ops.DEFAULT_LOG_MOVES, transitions=None,
                           log_weight=None, gap=None, seg_bonus=0.0, min_state=0, chunk_frames=None,
                           include_weight=False):
@@ -284,30 +318,11 @@ def segment_frames_warped(decoder, prototypes, frames, steps, log_moves=ops.DEFA
     it, its log weight, emissions, end-of-segment logits and moves), and
     ``last_state`` (int64: the step the segment ends in) and ``tempo`` (float64:
     ``(last_state + 1) / length``, prototype steps per frame)."""
-    # the plain arguments first: their errors need no device
-    mu, lv, offl = prototypes
-    T, s_min = int(steps), int(min_state)
-    if offl.dim() != 2 or not 1 <= T <= int(offl.shape[0]):
-        raise ValueError(f"segment_frames_warped: 1 <= steps <= the prototypes' {int(offl.shape[0])} steps, got {T}")
-    if not 0 <= s_min < T:
-        raise ValueError(f"segment_frames_warped: min_state must lie in 0 .. {T - 1}, got {s_min}")
-    K = int(offl.shape[1])
-    chunk = default_chunk_frames(T, K) if chunk_frames is None else int(chunk_frames)
-    if chunk < 1:
-        raise ValueError(f"segment_frames_warped: chunk_frames must be at least 1, got {chunk_frames}")
-    lm = list(ops._log_moves_arg("segment_frames_warped", log_moves))
-    if log_weight is not None and torch.as_tensor(log_weight).numel() != K:
-        raise ValueError(f"segment_frames_warped: log_weight must hold {K} entries, got "
-                         f"{torch.as_tensor(log_weight).numel()}")
-    N.require_gpu(frames)
-    n = int(frames.shape[0])
-    dev = frames.device
-    lw = None if log_weight is None else torch.as_tensor(log_weight, device=dev).float().reshape(-1)
-    if transitions is None:
-        lt, li, le = torch.zeros(K, K, device=dev), torch.zeros(K, device=dev), lw
-    else:
-        lt, li, _ = _chain_setup("segment_frames_warped", transitions, prototypes, dev)
-        le = lw if include_weight else None
+    offl = prototypes[2]
+    T, s_min, K, chunk, lm = _warped_plain_args("segment_frames_warped", prototypes, steps, min_state, chunk_frames,
+                                                log_moves, log_weight)
+    n, dev, lt, li, le = _warped_device_args("segment_frames_warped", prototypes, frames, transitions, log_weight,
+                                             include_weight, K)
     i64, f64 = dict(dtype=torch.int64, device=dev), dict(dtype=torch.float64, device=dev)
     if n == 0:
         return {"onset": torch.zeros(0, **i64), "length": torch.zeros(0, **i64), "category": torch.zeros(0, **i64),
@@ -483,6 +498,160 @@ def refit_transitions_em(posterior_fn, recordings, model, n_iter, pseudo_count, 
         totals.append(T * ev + c * pen)
         _m_step(model, tc, ic, c)
     return totals
+
+
+ALPHA_BUDGET_BYTES = 8 << 30  # segment_warp_posteriors(want_moves=True) keeps 8 N K steps bytes of aH: at most this
+
+
+def segment_warp_posteriors(decoder, prototypes, frames, steps, log_moves=ops.DEFAULT_LOG_MOVES, transitions=None,
+                            log_weight=None, gap=None, seg_bonus=0.0, min_state=0, chunk_frames=None,
+                            include_weight=False, temperature=1.0, want_counts=False, want_moves=False,
+                            with_segments=False):
+    """The sum half of ``segment_frames_warped``: the posterior over EVERY
+    cover, labelling and alignment of ``frames`` under the time-warped
+    programme, from a forward-backward over (frame, category, prototype step)
+    in fp64 on the device (``ops.warp_posterior_forward`` /
+    ``ops.warp_posterior_backward``).  The arguments are
+    ``segment_frames_warped``'s.  The emission plane is built ``chunk_frames``
+    frames at a time, ascending for the forward sweep and again descending for
+    the backward one, so peak plane memory is ``4 chunk_frames steps K`` bytes;
+    the carried state takes ``8 (5 (N + 1) K + 4 K steps + K K)`` bytes and a
+    little.  The result does not depend on ``chunk_frames``.  A dict of
+    ``segment_chain_posteriors``' keys,
+
+    ``log_evidence``        0-d float64; the TEMPERED model's when ``temperature != 1``
+    ``onset`` ``end`` ``gap``   N + 1 float64 each, summed over the categories
+    ``onset_by_category``   (N + 1) x K: P(a segment of k starts at frame n)
+    ``end_by_category``     (N + 1) x K: P(a segment of k ends before frame n)
+    ``frame_category``      N x K: P(frame n lies in a segment of k)
+    ``expected_segments``   0-d: the sum of ``end``
+    ``category_usage``      K: the expected number of segments of each category
+    ``no_segment``          0-d: P(the recording holds no segment at all)
+    ``trans_counts`` ``init_counts``  with ``want_counts``: the expected bigram (K x K) and first-label (K) counts
+    ``move_counts``         with ``want_moves``: K x 3, the expected stay / step / skip moves inside segments of k
+    ``expected_tempo``      with ``want_moves``: K, ``(step + 2 skip + usage) / (stay + step + skip + usage)``,
+                            the expected prototype steps per frame (NaN where category k is never used)
+
+    ``temperature`` divides every term (emissions, end-of-segment logits,
+    moves, log_enter, gap, bonus, log_trans, log_init) in float64 inside the
+    kernel.  ``want_moves`` keeps the forward sweep's aH plane, ``8 N K steps``
+    bytes, for the backward sweep; beyond ``ALPHA_BUDGET_BYTES`` (8 GiB) it
+    raises ValueError before any device work.  ``with_segments`` also runs
+    ``segment_frames_warped`` with the same arguments (at temperature 1) and
+    adds ``segmentation``, its dict bit for bit, and per chosen segment
+    ``onset_posterior`` and ``end_posterior`` (its category's onset / end
+    posterior at its first frame / behind its last) and ``occupancy`` (the mean
+    of ``frame_category`` over its frames in its category)."""
+    name = "segment_warp_posteriors"
+    T, s_min, K, chunk, lm = _warped_plain_args(name, prototypes, steps, min_state, chunk_frames, log_moves, log_weight)
+    temp = float(temperature)
+    if not (temp > 0.0 and math.isfinite(temp)):
+        raise ValueError(f"temperature must be positive, got {temperature}")
+    n = int(frames.shape[0])
+    if want_moves and 8 * n * K * T > ALPHA_BUDGET_BYTES:
+        raise ValueError(f"{name}: want_moves keeps 8 N K steps = {8 * n * K * T} bytes of the forward sweep, more "
+                         f"than ALPHA_BUDGET_BYTES = {ALPHA_BUDGET_BYTES}; cut the recording or raise the constant")
+    n, dev, lt, li, le = _warped_device_args(name, prototypes, frames, transitions, log_weight, include_weight, K)
+    f64 = dict(dtype=torch.float64, device=dev)
+    s = 1.0 / temp
+    want_counts, want_moves = bool(want_counts), bool(want_moves)
+    with torch.no_grad():
+        g = None if gap is None else torch.as_tensor(gap, device=dev).float()
+        v = prototypes[2][:T].reshape(-1)
+        state = ops.warp_posterior_state(n, K, T, dev)
+        alpha = torch.empty(n, K * T, **f64) if want_moves else None
+        args = (K, v, lm, le, g, float(seg_bonus), s, lt, li, s_min, state)
+        if n == 0:
+            cost = torch.empty(0, K * T, device=dev)
+            log_z = ops.warp_posterior_forward(cost, 0, 0, 0, *args, None)
+            post_k, gap_post, tc, ic, mc = ops.warp_posterior_backward(cost, 0, 0, 0, *args, alpha, want_counts,
+                                                                       want_moves)
+        starts = list(range(0, n, chunk))
+        for n0 in starts:
+            n1 = min(n, n0 + chunk)
+            cost = decoder.frame_costs(prototypes, frames, T, n0, n1)
+            log_z = ops.warp_posterior_forward(cost, n0, n1, n, *args, None if alpha is None else alpha[n0:n1])
+            del cost
+        for n0 in reversed(starts):
+            n1 = min(n, n0 + chunk)
+            cost = decoder.frame_costs(prototypes, frames, T, n0, n1)
+            post_k, gap_post, tc, ic, mc = ops.warp_posterior_backward(
+                cost, n0, n1, n, *args, None if alpha is None else alpha[n0:n1], want_counts, want_moves)
+            del cost
+        del alpha
+        onset_k, end_k = post_k[0], post_k[1]
+        reach = bool(log_z > -math.inf)
+        G_end = ops.warp_posterior_planes(state, n, K, T)["G"][n] if n > 0 else torch.zeros((), **f64)
+        no_seg = torch.exp(G_end - log_z) if reach else torch.zeros((), **f64)
+        usage = end_k.sum(0)
+        out = {"log_evidence": log_z, "onset": onset_k.sum(1), "end": end_k.sum(1), "gap": gap_post,
+               "onset_by_category": onset_k, "end_by_category": end_k,
+               "frame_category": torch.cumsum(onset_k - end_k, 0)[:n], "expected_segments": end_k.sum(),
+               "category_usage": usage, "no_segment": no_seg}
+        if want_counts:
+            out.update(trans_counts=tc, init_counts=ic)
+        if want_moves:
+            den = mc.sum(1) + usage
+            tempo = (mc[:, 1] + 2.0 * mc[:, 2] + usage) / den
+            out.update(move_counts=mc, expected_tempo=torch.where(den > 0, tempo, torch.full_like(den, math.nan)))
+    if with_segments:
+        seg = segment_frames_warped(decoder, prototypes, frames, steps, log_moves=log_moves, transitions=transitions,
+                                    log_weight=log_weight, gap=gap, seg_bonus=seg_bonus, min_state=min_state,
+                                    chunk_frames=chunk_frames, include_weight=include_weight)
+        on, ln, cat = seg["onset"], seg["length"], seg["category"]
+        out["segmentation"] = seg
+        out["onset_posterior"] = out["onset_by_category"][on, cat]
+        out["end_posterior"] = out["end_by_category"][on + ln, cat]
+        inside = torch.cat([torch.zeros(1, K, **f64), torch.cumsum(out["frame_category"], 0)])
+        out["occupancy"] = (inside[on + ln, cat] - inside[on, cat]) / ln.double()
+    return out
+
+
+def refit_warp_em(posterior_fn, recordings, model, log_moves, n_iter, pseudo_count, move_smoothing=1.0, fit_moves=True,
+                  temperature=1.0):
+    """EM of the time-warped programme's parameters on uncut recordings: the
+    ``TransitionModel`` (``model``; None: no matrix is fitted) and the moves
+    (stay, step, skip; ``fit_moves=False`` keeps them).  Per iteration
+    ``posterior_fn(recording, model, log_moves)`` (a
+    ``segment_warp_posteriors(..., want_counts=True, want_moves=True)`` result)
+    gives every recording's expected counts and log evidence; the counts are
+    summed, the matrix takes ``refit_transitions``' M-step with
+    ``pseudo_count`` and the moves take
+    ``alignment.moves_from_counts(move_counts.sum(0), move_smoothing,
+    log_moves)``, so a disabled move stays disabled.  Returns ``(totals,
+    log_moves)``: per iteration ``refit_transitions_em``'s objective,
+    ``temperature * sum log_evidence + pseudo_count * (sum of the finite
+    log_trans and log_init)``, under the parameters the iteration started
+    from, and the fitted moves.  ``model.last_counts`` keeps the final
+    iteration's ``(trans, init)`` expected counts."""
+    from . import alignment
+    c, T = float(pseudo_count), float(temperature)
+    lm = tuple(float(m) for m in log_moves)
+    totals = []
+    for _ in range(int(n_iter)):
+        K = None if model is None else model.K
+        tc = None if model is None else torch.zeros(K, K, dtype=torch.float64)
+        ic = None if model is None else torch.zeros(K, dtype=torch.float64)
+        mc = torch.zeros(3, dtype=torch.float64)
+        ev = 0.0
+        for rec in recordings:
+            out = posterior_fn(rec, model, lm)
+            ev += float(out["log_evidence"])
+            if model is not None:
+                tc += torch.as_tensor(out["trans_counts"]).double().cpu()
+                ic += torch.as_tensor(out["init_counts"]).double().cpu()
+            if fit_moves:
+                mc += torch.as_tensor(out["move_counts"]).double().cpu().sum(0)
+        pen = 0.0
+        if model is not None:
+            lt, li = model.log_trans.double().cpu(), model.log_init.double().cpu()
+            pen = float(lt[torch.isfinite(lt)].sum() + li[torch.isfinite(li)].sum())
+        totals.append(T * ev + c * pen)
+        if model is not None:
+            _m_step(model, tc, ic, c)
+        if fit_moves:
+            lm = alignment.moves_from_counts(mc, move_smoothing, lm)
+    return totals, lm
 
 
 def _tempered_posterior(table, d_min, gap, seg_bonus, temperature, want_table):

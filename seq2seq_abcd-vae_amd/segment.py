@@ -54,7 +54,13 @@ moves to the next or skips one with the probabilities ``--moves``, so a segment
 sung slower or faster than its prototype is still one segment.  ``--max_length``
 is then the number of prototype steps, not a bound on the segments' frames; the
 table gains ``last_state`` and ``tempo`` (prototype steps per frame), and
-``transition_score`` with ``--transitions``."""
+``transition_score`` with ``--transitions``.  ``--warp_posteriors`` sums over
+every cover, labelling and alignment under that programme
+(``segmentation.segment_warp_posteriors``) and appends ``onset_posterior``,
+``offset_posterior`` and ``occupancy``; ``--warp_refit N`` first runs N rounds of
+EM on the recordings (``segmentation.refit_warp_em``): the moves go to
+``--moves_out`` (``--keep_moves`` fixes them) and, with ``--transitions``, the
+matrix to ``--transitions_out``."""
 import os
 import sys
 
@@ -72,6 +78,8 @@ POSTERIOR_COLUMNS = ("onset_posterior", "offset_posterior", "span_posterior")   
 SYNTAX_COLUMNS = ("transition_score", "context_free_category_ix", "changed")      # appended by --transitions
 CHAIN_POSTERIOR_COLUMNS = POSTERIOR_COLUMNS + ("label_posterior",)                # appended by --chain_posteriors
 WARP_COLUMNS = ("last_state", "tempo")                                            # appended by --warp
+WARP_POSTERIOR_COLUMNS = ("onset_posterior", "offset_posterior", "occupancy")     # appended by --warp_posteriors
+MOVE_COLUMNS = ("stay", "step", "skip")                                           # --moves_out: one row of probabilities
 REFIT_METHODS = ("viterbi", "em")
 TRANSITION_COLUMNS = ("from_ix", "to_ix", "probability", "expected_count")       # sequence.py's transitions.csv
 RECORDING_COLUMNS = ("input_path", "n_frames", "n_segments", "path_score", "log_evidence", "expected_segments")
@@ -120,13 +128,15 @@ def covered_frames(n_frames, onsets, offsets, fs, frame, hop, centering=True):
 
 
 def segment_rows(input_path, onset, length, category, score, fs, frame, hop, centering, total, data_type="segmented",
-                 speaker=float("nan"), posteriors=None, syntax=None, chain_posteriors=None, warp=None):
+                 speaker=float("nan"), posteriors=None, syntax=None, chain_posteriors=None, warp=None,
+                 warp_posteriors=None):
     """The table rows of one recording's segments (frame units -> seconds);
     ``posteriors``: the three per-segment lists of POSTERIOR_COLUMNS;
     ``syntax``: (link, context-free category) per segment for SYNTAX_COLUMNS;
     ``chain_posteriors``: the four per-segment lists of CHAIN_POSTERIOR_COLUMNS;
     ``warp``: (last state, tempo, link or None) per segment for WARP_COLUMNS
-    and, with a link, ``transition_score``."""
+    and, with a link, ``transition_score``; ``warp_posteriors``: the three
+    per-segment lists of WARP_POSTERIOR_COLUMNS."""
     rows = []
     for i, (s, d, k, v) in enumerate(zip(onset, length, category, score)):
         on, off = frames_to_samples(s, d, frame, hop, centering, total)
@@ -146,11 +156,14 @@ def segment_rows(input_path, onset, length, category, score, fs, frame, hop, cen
             rows[-1].update({"last_state": int(last[i]), "tempo": float(tempo[i])})
             if link is not None:
                 rows[-1]["transition_score"] = float(link[i])
+        if warp_posteriors is not None:
+            rows[-1].update({c: float(p[i]) for c, p in zip(WARP_POSTERIOR_COLUMNS, warp_posteriors)})
     return rows
 
 
 def write_segments(save_path, rows, posteriors=False, recordings_out=None, recordings=(), curves=None, syntax=False,
-                   transitions_out=None, transitions=None, chain_posteriors=False, warp=False):
+                   transitions_out=None, transitions=None, chain_posteriors=False, warp=False,
+                   warp_posteriors=False, moves_out=None, moves=None):
     """Writes the annotation table (an existing file is kept as .prev, nothing
     partial is left behind) and, with ``posteriors``, its three extra columns,
     the per-recording table and the per-recording curve files ({path: dict of
@@ -158,18 +171,22 @@ def write_segments(save_path, rows, posteriors=False, recordings_out=None, recor
     ``transitions`` (a table in TRANSITION_COLUMNS) to ``transitions_out``;
     with ``chain_posteriors`` the CHAIN_POSTERIOR_COLUMNS after those; with
     ``warp`` the WARP_COLUMNS (and, with ``syntax``, ``transition_score`` alone
-    of the SYNTAX_COLUMNS: the warped programme has no context-free label).
-    Returns the number of rows."""
+    of the SYNTAX_COLUMNS: the warped programme has no context-free label);
+    with ``warp_posteriors`` the WARP_POSTERIOR_COLUMNS last, and ``moves``
+    (three probabilities) to ``moves_out``.  Returns the number of rows."""
     df = pd.DataFrame(rows, columns=list(COLUMNS) + (list(POSTERIOR_COLUMNS) if posteriors else []) +
                       (list(WARP_COLUMNS) if warp else []) +
                       (list(SYNTAX_COLUMNS[:1] if warp else SYNTAX_COLUMNS) if syntax else []) +
-                      (list(CHAIN_POSTERIOR_COLUMNS) if chain_posteriors else []))
+                      (list(CHAIN_POSTERIOR_COLUMNS) if chain_posteriors else []) +
+                      (list(WARP_POSTERIOR_COLUMNS) if warp_posteriors else []))
     with cli.replacing_outputs() as tmp:
         df.to_csv(tmp(save_path), index=False)
         if recordings_out is not None:
             pd.DataFrame(list(recordings), columns=list(RECORDING_COLUMNS)).to_csv(tmp(recordings_out), index=False)
         if transitions_out is not None:
             transitions.to_csv(tmp(transitions_out), index=False)
+        if moves_out is not None:
+            pd.DataFrame([list(moves)], columns=list(MOVE_COLUMNS)).to_csv(tmp(moves_out), index=False)
         for path, arrays in (curves or {}).items():
             with open(tmp(path), "wb") as f:
                 np.savez(f, **arrays)
@@ -222,6 +239,18 @@ class Segmenter(classify.Classifier):
                                                   log_moves=log_moves, transitions=transitions, log_weight=log_weight,
                                                   gap=gap, seg_bonus=seg_bonus, min_state=min_state,
                                                   chunk_frames=chunk_frames)
+
+    def warp_posteriors(self, frames, steps, log_moves, min_state=0, log_weight=None, gap=None, seg_bonus=0.0,
+                        speaker=None, transitions=None, chunk_frames=None, **kw):
+        """``segmentation.segment_warp_posteriors`` of one recording's frames
+        under the categories' prototypes decoded for ``steps`` steps."""
+        if self.decoder.embed_speaker is not None and speaker is None:
+            raise ValueError("this decoder embeds speakers: a speaker index is required")
+        protos = self.prototypes_for([0 if speaker is None else int(speaker)], int(steps))
+        return segmentation.segment_warp_posteriors(self.decoder, protos, frames.to(self.device), int(steps),
+                                                    log_moves=log_moves, transitions=transitions,
+                                                    log_weight=log_weight, gap=gap, seg_bonus=seg_bonus,
+                                                    min_state=min_state, chunk_frames=chunk_frames, **kw)
 
     def chain_posteriors(self, frames, max_length, transitions, min_length=1, log_weight=None, gap=None,
                          seg_bonus=0.0, speaker=None, **kw):
@@ -312,8 +341,36 @@ def get_parameters(argv=None):
     p.add_argument("--chunk_frames", type=int, default=None,
                    help="with --warp: frames of the emission plane built at a time, 4 chunk_frames max_length K bytes "
                         "(default: as many as fit 256 MiB); the result does not depend on it")
+    p.add_argument("--warp_posteriors", action="store_true",
+                   help="with --warp: also sum over every cover, labelling and alignment under the time-warped "
+                        "programme and append onset_posterior, offset_posterior and occupancy (the mean probability "
+                        "that the segment's frames lie in a segment of its category); --posterior_temperature, "
+                        "--curves_dir and --recordings_out apply as with --chain_posteriors")
+    p.add_argument("--warp_refit", type=int, default=0,
+                   help="with --warp: iterations of EM on the recordings before the final cut (0: none): the moves "
+                        "are refitted from their expected counts and written to --moves_out, and with --transitions "
+                        "the matrix from its expected bigram counts, written to --transitions_out")
+    p.add_argument("--moves_out", type=str, default=None,
+                   help="where --warp_refit writes the refitted moves (csv: stay, step, skip probabilities)")
+    p.add_argument("--keep_moves", action="store_true",
+                   help="with --warp_refit: keep --moves as given and refit the matrix only")
     a = p.parse_args(argv)
     cli.check_moves_argument(p, a)
+    if not a.warp and (a.warp_posteriors or a.warp_refit != 0):
+        p.error("--warp_posteriors and --warp_refit need --warp")
+    if a.warp_refit < 0:
+        p.error("--warp_refit must not be negative")
+    if a.warp_refit == 0 and (a.moves_out is not None or a.keep_moves):
+        p.error("--moves_out and --keep_moves need --warp_refit")
+    if a.warp_refit > 0:
+        if a.keep_moves == (a.moves_out is not None):
+            p.error("--warp_refit writes the refitted moves to --moves_out; give --moves_out, or --keep_moves to "
+                    "fix the moves, not both")
+        if a.keep_moves and a.transitions is None:
+            p.error("--warp_refit with --keep_moves has nothing to fit without --transitions")
+        if (a.transitions is not None) != (a.transitions_out is not None):
+            p.error("--warp_refit refits the matrix of --transitions and writes it to --transitions_out: the two go "
+                    "together")
     if a.warp:
         for flag, on in (("--posteriors", a.posteriors), ("--chain_posteriors", a.chain_posteriors),
                          ("--window_frames", a.window_frames is not None),
@@ -344,14 +401,14 @@ def get_parameters(argv=None):
         p.error("--refit_method needs --refit_transitions")
     if a.refit_transitions < 0:
         p.error("--refit_transitions must not be negative")
-    if (a.refit_transitions > 0) != (a.transitions_out is not None):
+    if a.warp_refit <= 0 and (a.refit_transitions > 0) != (a.transitions_out is not None):
         p.error("--refit_transitions and --transitions_out go together")
     if a.posteriors and (a.transitions is not None or a.refit_transitions > 0):
         p.error("--transitions / --refit_transitions cannot be combined with --posteriors: posteriors under a "
                 "transition model are not available")
     if not a.posterior_temperature > 0:
         p.error("--posterior_temperature must be positive")
-    if not (a.posteriors or a.chain_posteriors) and (a.posterior_temperature != 1.0 or a.curves_dir is not None
+    if not (a.posteriors or a.chain_posteriors or a.warp_posteriors) and (a.posterior_temperature != 1.0 or a.curves_dir is not None
                                                      or a.recordings_out is not None):
         p.error("--posterior_temperature, --curves_dir and --recordings_out need --posteriors")
     if a.max_length < 1 or a.max_length > 16383:
@@ -369,7 +426,7 @@ def get_parameters(argv=None):
 def main(argv=None):
     a = get_parameters(argv)
     save_path = a.save_path or os.path.join(a.input_root, "segmented.csv")
-    for path in (save_path, a.gap_model_out, a.recordings_out, a.transitions_out):
+    for path in (save_path, a.gap_model_out, a.recordings_out, a.transitions_out, a.moves_out):
         if path and os.path.dirname(path):
             os.makedirs(os.path.dirname(path), exist_ok=True)
     if a.curves_dir:
@@ -410,6 +467,7 @@ def main(argv=None):
     lw = seg.log_weight(a.prior, len(table) if a.entire_data_size is None else a.entire_data_size)
     syntax = a.transitions is not None or a.refit_transitions > 0
     model, trans_table, prepared, warned = None, None, {}, []
+    log_moves = alignment.moves_from_probabilities(a.moves) if a.warp else None
 
     def prepare(path):
         if path in prepared:
@@ -427,25 +485,29 @@ def main(argv=None):
         elif gap_model is not None:
             gap = segmentation.gap_scores(frames, *gap_model)
         got = (fs, frame, hop, total, frames, d_min, gap)
-        if a.refit_transitions > 0:     # the training passes and the final cut share the features
+        if a.refit_transitions > 0 or a.warp_refit > 0:     # the training passes and the final cut share the features
             prepared[path] = got
         return got
+
+    def warp_min_state(path, d_min):
+        """--min_state raised so that every segment has the d_min frames the loader needs."""
+        # a segment that ends in state s has at least s / (the largest advance) + 1 frames
+        stride = 2 if a.moves[2] > 0 else 1
+        s_min = max(a.min_state, stride * (d_min - 1))
+        if s_min > a.min_state and not warned:
+            warned.append(s_min)
+            print(f"--min_state raised from {a.min_state} to {s_min}: every segment then has the {d_min} frames "
+                  "the loader can featurise", file=sys.stderr)
+        if s_min >= a.max_length:
+            raise SystemExit(f"{path}: --max_length {a.max_length} leaves no state >= {s_min} to end in")
+        return s_min
 
     def cut(path, transitions=None, got=None):
         _, _, _, _, frames, d_min, gap = got or prepare(path)
         if a.warp:
-            # a segment that ends in state s has at least s / (the largest advance) + 1 frames
-            stride = 2 if a.moves[2] > 0 else 1
-            s_min = max(a.min_state, stride * (d_min - 1))
-            if s_min > a.min_state and not warned:
-                warned.append(s_min)
-                print(f"--min_state raised from {a.min_state} to {s_min}: every segment then has the {d_min} frames "
-                      "the loader can featurise", file=sys.stderr)
-            if s_min >= a.max_length:
-                raise SystemExit(f"{path}: --max_length {a.max_length} leaves no state >= {s_min} to end in")
-            return seg.segment_recording_warped(frames, a.max_length, alignment.moves_from_probabilities(a.moves),
-                                                min_state=s_min, log_weight=lw, gap=gap, seg_bonus=a.segment_bonus,
-                                                speaker=a.speaker, transitions=transitions,
+            return seg.segment_recording_warped(frames, a.max_length, log_moves,
+                                                min_state=warp_min_state(path, d_min), log_weight=lw, gap=gap,
+                                                seg_bonus=a.segment_bonus, speaker=a.speaker, transitions=transitions,
                                                 chunk_frames=a.chunk_frames)
         return seg.segment_recording(frames, a.max_length, min_length=d_min, log_weight=lw, gap=gap,
                                      seg_bonus=a.segment_bonus, speaker=a.speaker, posteriors=a.posteriors,
@@ -456,6 +518,12 @@ def main(argv=None):
         _, _, _, _, frames, d_min, gap = got or prepare(path)
         return seg.chain_posteriors(frames, a.max_length, transitions, min_length=d_min, log_weight=lw, gap=gap,
                                     seg_bonus=a.segment_bonus, speaker=a.speaker, **kw)
+
+    def warp_posterior(path, transitions, moves, got=None, **kw):
+        _, _, _, _, frames, d_min, gap = got or prepare(path)
+        return seg.warp_posteriors(frames, a.max_length, moves, min_state=warp_min_state(path, d_min), log_weight=lw,
+                                   gap=gap, seg_bonus=a.segment_bonus, speaker=a.speaker, transitions=transitions,
+                                   chunk_frames=a.chunk_frames, **kw)
 
     if syntax:
         import sequence
@@ -473,12 +541,25 @@ def main(argv=None):
             totals = segmentation.refit_transitions(cut, paths, model, a.refit_transitions, 1.0 / K)
             for i, v in enumerate(totals):
                 print(f"refit iteration {i}: summed path score {v:.6f}", file=sys.stderr)
-        if a.refit_transitions > 0:
+        if a.warp_refit > 0:
+            totals, log_moves = segmentation.refit_warp_em(
+                lambda path, m, moves: warp_posterior(path, m, moves, want_counts=True, want_moves=not a.keep_moves),
+                paths, model, log_moves, a.warp_refit, 1.0 / K, fit_moves=not a.keep_moves)
+            for i, v in enumerate(totals):
+                print(f"warp refit iteration {i}: log posterior of the matrix and the moves {v:.6f}", file=sys.stderr)
+        if a.refit_transitions > 0 or a.warp_refit > 0:
             ft, tt = np.divmod(np.arange(K * K), K)
             trans_table = pd.DataFrame({"from_ix": ft, "to_ix": tt,
                                         "probability": model.log_trans.double().exp().reshape(-1).cpu().numpy(),
                                         "expected_count": model.last_counts[0].reshape(-1).cpu().numpy()},
                                        columns=list(TRANSITION_COLUMNS))
+
+    if a.warp_refit > 0 and not syntax:
+        totals, log_moves = segmentation.refit_warp_em(
+            lambda path, m, moves: warp_posterior(path, m, moves, want_moves=True), paths, None, log_moves,
+            a.warp_refit, 0.0)
+        for i, v in enumerate(totals):
+            print(f"warp refit iteration {i}: summed log evidence {v:.6f}", file=sys.stderr)
 
     rows, recordings, curves = [], [], {}
     for path in paths:
@@ -487,6 +568,10 @@ def main(argv=None):
         post = None
         if a.chain_posteriors:
             post = posterior(path, model, got, temperature=a.posterior_temperature, with_segments=True)
+            out = post["segmentation"]
+        elif a.warp_posteriors:
+            post = warp_posterior(path, model, log_moves, got, temperature=a.posterior_temperature,
+                                  with_segments=True)
             out = post["segmentation"]
         else:
             out = cut(path, model, got)
@@ -505,7 +590,9 @@ def main(argv=None):
                              if syntax and not a.warp else None,
                              warp=(out["last_state"].tolist(), out["tempo"].tolist(),
                                    out["link"].tolist() if syntax else None) if a.warp else None,
-                             chain_posteriors=None if post is None else [
+                             warp_posteriors=[post[c].tolist() for c in ("onset_posterior", "end_posterior",
+                                                                         "occupancy")] if a.warp_posteriors else None,
+                             chain_posteriors=None if post is None or a.warp_posteriors else [
                                  post["onset"][out["onset"]].tolist(),
                                  post["end"][out["onset"] + out["length"]].tolist(),
                                  post["span_posterior"].tolist(), post["label_posterior"].tolist()])
@@ -530,7 +617,9 @@ def main(argv=None):
     _native.op_status.sync("segment")
     write_segments(save_path, rows, posteriors=a.posteriors, recordings_out=a.recordings_out, recordings=recordings,
                    curves=curves, syntax=syntax, transitions_out=a.transitions_out, transitions=trans_table,
-                   chain_posteriors=a.chain_posteriors, warp=a.warp)
+                   chain_posteriors=a.chain_posteriors, warp=a.warp, warp_posteriors=a.warp_posteriors,
+                   moves_out=a.moves_out if a.warp_refit > 0 and not a.keep_moves else None,
+                   moves=None if log_moves is None else [float(np.exp(m)) for m in log_moves])
     return save_path
 
 
